@@ -4,9 +4,17 @@ MI355X, BASELINE.json metric.  Default workload: configs[3] = 1024x1024x12 fd_gr
 
 A "step" = one LSQR iteration on the device-resident system (SpMV + SpMTV + fused vector
 updates + two device reductions).  Timed: exactly K iterations after W warm-up iterations,
-bracketed by barrier + device synchronisation, max over ranks.  Also reported: a full solve
+bracketed by barrier + device synchronisation, max over ranks.  A plain run does only that:
+set-up, warm-up, the K timed steps, the result line.  With --full it also reports a full solve
 to tolerance (solve_time_s, solve_iters), the per-kernel roofline of the dominant kernel
-(HIP-event timed), and the oracle's CPU LSQR on a bounded sample of iterations on this host.
+(HIP-event timed, rocprofv3 PMC traffic), and the oracle's CPU solver on a bounded sample of
+iterations on this host.
+
+--dump-outputs DIR writes what the timed call returned after its last step as
+DIR/iterate_stats.npy (float64, DUMP_FIELDS order): the iteration count and the residual,
+operator, gradient and solution norms of the iterate reached after W + K iterations.  The
+synthetic inputs are seeded, so two builds run with the same arguments can be compared
+output for output.
 
 N > 1 (torchrun): see DESIGN.md §Multi-GPU.
 """
@@ -23,6 +31,9 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec (MI355X_MICROARCH.md chip table)
 ANISO = ('c5a', 'ta64', 'ta100')   # lssurf_amd.synthetic.ANISO (no package import before the PMC passes)
+# --dump-outputs: the computed fields of the timed call's statistics, in this order (timings and
+# the byte model are not outputs of the computation)
+DUMP_FIELDS = ('iters', 'istop', 'method', 'r1norm', 'r2norm', 'anorm', 'acond', 'arnorm', 'xnorm')
 
 
 def log(*a):
@@ -288,20 +299,32 @@ def e2e(config, iters):
                       'n_edited': int(np.sum(S['data'].three_sigma_edit == 0))}), flush=True)
 
 
+def dump_outputs(path, st):
+    """--dump-outputs: what the timed call returned after its last step, DIR/iterate_stats.npy."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'iterate_stats.npy'), np.array([float(st[k]) for k in DUMP_FIELDS], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--config', default='c4')
-    ap.add_argument('--no-solve', action='store_true', help='skip the full solve to tolerance')
+    ap.add_argument('--full', action='store_true',
+                    help='beside the timed steps: the full solves to tolerance, the per-kernel roofline with the '
+                         'rocprofv3 PMC traffic passes and the CPU baseline (each has a --no-... switch)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed call returned after its last step as DIR/iterate_stats.npy '
+                         '(float64: ' + ', '.join(DUMP_FIELDS) + ')')
+    ap.add_argument('--no-solve', action='store_true', help='--full: skip the full solve to tolerance')
     ap.add_argument('--cpu-iters', type=int, default=80,
                     help='iterations of the CPU baseline sample (the GPU line\'s algorithm: CGNR + block-Jacobi, or LSQR)')
-    ap.add_argument('--no-cpu', action='store_true')
+    ap.add_argument('--no-cpu', action='store_true', help='--full: skip the CPU baseline')
     ap.add_argument('--cpu-solve', action='store_true',
                     help='also run the CPU oracle LSQR to the solve tolerance (BASELINE.md §4 parity at size; slow)')
     ap.add_argument('--dist', action='store_true', help='use the distributed (RCCL) path even at N=1')
-    ap.add_argument('--no-pmc', action='store_true', help='skip the rocprofv3 PMC traffic passes')
+    ap.add_argument('--no-pmc', action='store_true', help='--full: skip the rocprofv3 PMC traffic passes')
     ap.add_argument('--op', type=int, default=0, help='0: auto (structured stencil operator), 1: assembled SELL')
     ap.add_argument('--same-device', action='store_true',
                     help='testing only: every rank on device 0 (RCCL over loopback sockets, distinct host ids)')
@@ -316,6 +339,8 @@ def main():
     ap.add_argument('--e2e', type=int, default=0, metavar='ITERS',
                     help='instead of the bench line: time smooth_fit end to end with max_iterations=ITERS')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     if args.e2e:
         return e2e(args.config, args.e2e)
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -329,7 +354,7 @@ def main():
     if args.pmc_child:
         return pmc_child(args.config, args.op, meth, args.precond)
     pmc, pmc_note = None, 'skipped (--no-pmc, --dist or N>1)'
-    if world == 1 and not args.no_pmc and not args.dist:
+    if args.full and world == 1 and not args.no_pmc and not args.dist:
         pmc, pmc_note = pmc_traffic(args.config, args.op, meth, args.precond)   # child processes, before this one touches the GPU
 
     rank = int(os.environ.get('RANK', '0'))
@@ -406,22 +431,30 @@ def main():
     if isinstance(solver, _Dist):
         gn = int(fs.keep_cols.size)
     bytes_iter = st['bytes_per_iter']
+    if args.dump_outputs and rank == 0:   # the norms are all-reduced: every rank holds the same
+        dump_outputs(args.dump_outputs, st)
 
-    if meth == 1:
-        prof = solver.profile_cg(reps=10, precond=args.precond)
-        roles = ('cg_data', 'cg_normal', 'cg_update')
-    else:
-        prof = solver.profile_kernels(reps=10, op=args.op)
-        roles = ('spmtv', 'xw_spmv')
-    # algorithmic bytes per launch (DESIGN.md §Byte model)
-    kb = prof.pop('bytes')   # algorithmic bytes per launch, from the library's byte model
-    data_rows = prof.pop('data_rows', None)   # CGNR: 'matrix-free' (points sorted by cell) or 'stored'
-    normal_kernel = prof.pop('normal_kernel', None)   # CGNR: 'wave-strip' (k_cg_normal_rw) or 'ring'
-    dom = max(roles, key=lambda k: prof[k])
-    achieved = kb[dom] / (prof[dom] * 1e-3) / 1e9
+    roofline, data_rows, normal_kernel = None, None, None
+    if args.full:   # the per-kernel profile launches runs of its own on the iteration state
+        if meth == 1:
+            prof = solver.profile_cg(reps=10, precond=args.precond)
+            roles = ('cg_data', 'cg_normal', 'cg_update')
+        else:
+            prof = solver.profile_kernels(reps=10, op=args.op)
+            roles = ('spmtv', 'xw_spmv')
+        # algorithmic bytes per launch (DESIGN.md §Byte model)
+        kb = prof.pop('bytes')   # algorithmic bytes per launch, from the library's byte model
+        data_rows = prof.pop('data_rows', None)   # CGNR: 'matrix-free' (points sorted by cell) or 'stored'
+        normal_kernel = prof.pop('normal_kernel', None)   # CGNR: 'wave-strip' (k_cg_normal_rw) or 'ring'
+        dom = max(roles, key=lambda k: prof[k])
+        achieved = kb[dom] / (prof[dom] * 1e-3) / 1e9
+        traffic, traffic_note = (pmc[dom]['total'], pmc) if pmc else (None, pmc_note)
+        roofline = {'bound': 'hbm', 'kernel': dom, 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                    'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic,
+                    'algorithmic_bytes': kb[dom], 'traffic_detail': traffic_note, 'kernel_ms': prof}
 
     solve = {}
-    if not args.no_solve:
+    if args.full and not args.no_solve:
         # solve wall-time with smooth_fit's default solver for this system: CGNR + the multigrid
         # V-cycle (precond 4) where it runs (per-node blocks; over ranks: window level 0 + the
         # replicated global coarse levels), else the timed configuration; then CGNR + block-Jacobi
@@ -474,7 +507,7 @@ def main():
         for r, b in zip(ranks, gather(solve['solve_comm_bytes_per_iter'])):
             r['solve_comm_bytes_per_iter'] = b
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu and not args.dist:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and not args.dist:
         hc = host_cores()
         threads = hc['usable']   # every core this process may use, one OpenMP thread per core, pinned
         os.environ.setdefault('OMP_PROC_BIND', 'close')   # read by libgomp when oracle/_cpu.so loads
@@ -499,7 +532,6 @@ def main():
                         'solve_rel_diff_gpu_vs_cpu': float(np.linalg.norm(x - xc) / np.linalg.norm(xc))})
     fs.close()
 
-    traffic, traffic_note = (pmc[dom]['total'], pmc) if pmc else (None, pmc_note)
     method_name = {0: 'LSQR', 1: 'CGNR (PCG on AᵀA)'}[int(st.get('method', meth))]
 
     if rank == 0:
@@ -515,7 +547,9 @@ def main():
                                    + (' (directional z0 constraint, aniso notebook)' if args.config in ANISO else ''),
                        'rank0_system': info, 'rows': gm, 'cols': gn,
                        'nnz': gZ, 'precond': {1: 'column scaling', 3: 'block-Jacobi per (y,x) node'}.get(args.precond, args.precond),
-                       'operator': ('structured stencil rows + ' + ('matrix-free data rows (points sorted by cell)'
+                       # the data rows' kind and the normal kernel are read off the per-kernel profile (--full)
+                       'operator': ('structured stencil rows' if data_rows is None else
+                                    'structured stencil rows + ' + ('matrix-free data rows (points sorted by cell)'
                                                                      if data_rows == 'matrix-free' else 'SELL data rows'))
                        if (fs.structured if isinstance(solver, _Dist) else info.get('stencil_op') and args.op == 0)
                        else 'assembled SELL',
@@ -523,10 +557,7 @@ def main():
                        'parallelism': f'y-slab rows x{world} (RCCL)' if world > 1 or args.dist else 'single'},
             'device_iter_ms': 1e3 * t_dev / args.steps,
             'hbm_gbs_iter': bytes_iter * args.steps / t_dev / 1e9,
-            'roofline': {'bound': 'hbm', 'kernel': dom, 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                         'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic,
-                         'algorithmic_bytes': kb[dom], 'traffic_detail': traffic_note, 'kernel_ms': prof},
-            'cpu_baseline': cpu,
+            'full': bool(args.full), 'roofline': roofline, 'cpu_baseline': cpu,
             **solve, **setup,
         }
         if ranks is not None:

@@ -10,14 +10,14 @@ CFG=${2:-c4}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$GRAFT_REPO_ROOT"
-timeout -k 10 600 python3 bench.py --config "$CFG" > "$OUT/bench.json" 2> "$OUT/bench.err"
-timeout -k 10 300 python3 bench.py --config "$CFG" --dist --no-cpu --no-pmc > "$OUT/bench_dist1.json" 2> "$OUT/bench_dist1.err"
+timeout -k 10 600 python3 bench.py --full --config "$CFG" > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 300 python3 bench.py --full --config "$CFG" --dist --no-cpu --no-pmc > "$OUT/bench_dist1.json" 2> "$OUT/bench_dist1.err"
 export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/ktrace" -o run --output-format csv -- \
     python3 "$GRAFT_REPO_ROOT/bench.py" --config "$CFG" --steps 100 --warmup 10 --no-cpu --no-solve --no-pmc \
     > "$OUT/ktrace.json" 2> "$OUT/ktrace.err"
 timeout -k 10 600 python3 bench.py --config "$CFG" --e2e 3 > "$OUT/e2e.json" 2> "$OUT/e2e.err"
 timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-    --master-port 29533 bench.py --gpus 2 --same-device --config "$CFG" --steps 100 --warmup 10 \
+    --master-port 29533 bench.py --full --gpus 2 --same-device --config "$CFG" --steps 100 --warmup 10 \
     > "$OUT/bench_n2_same_device.json" 2> "$OUT/bench_n2_same_device.err"
 echo done > "$OUT/ok"

@@ -18,6 +18,7 @@ sys_*.npz      for each smooth_fit / lin_op configuration: the input points, the
                sigma_extra, dzdt_lag1, E sigma grids)
 tri.npz        I/O of the reference Cython kernels inv_tr_upper / propagate_qz_errors /
                spsolve_tr_upper on random upper-triangular CSR matrices (incl. overflow)
+tri_random.npz inv_tr_upper with an N² buffer on two more random matrices (diagonal down to 0.5)
 sys_avg.npz    averaging products (avg_scales, z0_average_scale, avg_masks) and their errors
 kat.npz        the analytic amplitude KAT of notebooks/smooth_fit_demo.ipynb cell 8
 sys_sekeys.npz sigma_extra_keys: per-group sigma_extra from a data field (smooth_fit.py:442-447)
@@ -490,6 +491,27 @@ def gen_tri(LS):
     print('tri: ok')
 
 
+def gen_tri_random(LS):
+    """inv_tr_upper with a buffer that always fits (N² entries) on the random matrices of
+    test_oracle.test_tri_oracle_vs_live_reference_random: the matrices and the kernel's outputs."""
+    import importlib
+    itu = importlib.import_module('LSsurf.inv_tr_upper').inv_tr_upper
+    rng = np.random.default_rng(5)
+    out = {}
+    cases = [(40, 0.2), (120, 0.05)]
+    for i, (N, dens) in enumerate(cases):
+        R = sp.triu(sp.random(N, N, density=dens, random_state=rng), k=1).tocsr() + \
+            sp.diags(rng.uniform(0.5, 2, N) * np.sign(rng.normal(size=N)))
+        R = sp.csr_matrix(R)
+        R.sort_indices()
+        out.update(_csr_arrays(f'R{i}', R))
+        rr, cc, vv, st = itu(R, N * N, 1e-5)
+        out[f'inv{i}_rr'], out[f'inv{i}_cc'], out[f'inv{i}_vv'], out[f'inv{i}_st'] = rr, cc, vv, np.array(st)
+    out['ncases'] = np.array(len(cases))
+    np.savez_compressed(os.path.join(HERE, 'tri_random.npz'), **out)
+    print('tri_random: ok')
+
+
 def gen_kat(LS):
     """notebooks/smooth_fit_demo.ipynb cells 4-8: recovered vs analytic sine amplitude."""
     import pointCollection as pc
@@ -526,7 +548,8 @@ def main():
     import _refstubs
     LS = _refstubs.install()
     sys.modules['LSsurf.smooth_fit'].smooth_fit   # module (LSsurf/__init__.py:6 rebinds the name)
-    gens = {'stencils': lambda: gen_stencils(LS), 'tri': lambda: gen_tri(LS), 'lin2d': lambda: gen_lin2d(LS),
+    gens = {'stencils': lambda: gen_stencils(LS), 'tri': lambda: gen_tri(LS), 'tri_random': lambda: gen_tri_random(LS),
+            'lin2d': lambda: gen_lin2d(LS),
             'systems': lambda: gen_systems(LS, _refstubs), 'avg': lambda: gen_avg(LS, _refstubs),
             'kat': lambda: gen_kat(LS), 'aniso': lambda: gen_aniso(LS, _refstubs),
             'eq_edit': lambda: gen_eq_edit(LS, _refstubs), 'tide': lambda: gen_tide(LS, _refstubs),

@@ -7,7 +7,6 @@ import os
 
 import numpy as np
 import pytest
-import scipy.sparse as sp
 
 from conftest import ROOT, SYSTEMS, golden, golden_csr
 from oracle import cpu, dense
@@ -48,20 +47,23 @@ def _load_ref(name):
 
 
 def test_tri_oracle_vs_live_reference_random():
+    """The oracle's inv_tr_upper against the reference kernel's on the random matrices drawn from
+    default_rng(5) (N = 40 at density 0.2, N = 120 at 0.05, an N² buffer), bit for bit: against
+    the kernel's stored outputs (tri_random.npz: the matrices and what the reference returned,
+    gen_golden.py gen_tri_random) and, where oracle/_ref was built, against the live kernel too."""
+    d = golden('tri_random.npz')
     itu = _load_ref('inv_tr_upper')
-    if itu is None:
-        pytest.skip('oracle/_ref not built')
-    rng = np.random.default_rng(5)
-    for N, dens in [(40, 0.2), (120, 0.05)]:
-        R = sp.triu(sp.random(N, N, density=dens, random_state=rng), k=1).tocsr() + \
-            sp.diags(rng.uniform(0.5, 2, N) * np.sign(rng.normal(size=N)))
-        R = sp.csr_matrix(R)
-        R.sort_indices()
-        a = itu.inv_tr_upper(R, N * N, 1e-5)
+    for i, N in enumerate([40, 120]):
+        R = golden_csr(d, f'R{i}')
+        assert R.shape == (N, N)
+        refs = [(d[f'inv{i}_rr'], d[f'inv{i}_cc'], d[f'inv{i}_vv'], int(d[f'inv{i}_st']))]
+        if itu is not None:
+            refs.append(itu.inv_tr_upper(R, N * N, 1e-5))
         b = cpu.inv_tr_upper(R, N * N, 1e-5)
-        for x, y in zip(a[:3], b[:3]):
-            np.testing.assert_array_equal(x, y)
-        assert a[3] == b[3]
+        for a in refs:
+            for x, y in zip(a[:3], b[:3]):
+                np.testing.assert_array_equal(x, y)
+            assert a[3] == b[3]
 
 
 @pytest.mark.parametrize('name', SYSTEMS + ['lin2d'])

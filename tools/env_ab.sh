@@ -13,7 +13,7 @@ for i in 1 2; do
     if [ $side = a ]; then E=$A; else E=$B; fi
     for c in $CFGS; do
       if [ $c = c4 ] || [ $c = c5 ]; then F=""; else F="--dist"; fi
-      env $E timeout -k 10 300 python3 bench.py --config $c $F --no-cpu --no-pmc --steps 300 --warmup 20 \
+      env $E timeout -k 10 300 python3 bench.py --full --config $c $F --no-cpu --no-pmc --steps 300 --warmup 20 \
         > $OUT/${c}_${side}_$i.json 2> $OUT/${c}_${side}_$i.err
     done
   done
