@@ -386,8 +386,30 @@ int lsq_fence_selftest(int32_t n, int32_t fail_rank, int32_t rounds);
 typedef struct lsq_rde lsq_rde;
 lsq_rde* lsq_rde_create(int32_t device, int64_t n, const double* r, const double* sigma);
 int lsq_rde_order_stats(lsq_rde* c, double sigma_extra, int64_t n_idx, const int64_t* idx, double* out);
-const char* lsq_rde_last_error(lsq_rde* c);
+const char* lsq_rde_last_error(lsq_rde* c);     /* c = NULL: why the last create_segments failed */
 void lsq_rde_destroy(lsq_rde* c);
+
+/* Binned sigma_extra (calc_sigma_extra_on_grid.py): many overlapping segments of one point set —
+ * segment k = the points seg_idx[seg_ptr[k] .. seg_ptr[k+1]) (seg_ptr[0] = 0, fewer than 2^31
+ * entries in all) — each with its four 0-based ranks seg_rank[4k..4k+4) = (j_lo, j_lo+1, j_hi,
+ * j_hi+1).  lsq_rde_create_segments keeps segment-contiguous copies of r and σ on the device.
+ * status (nullable): 0, -2 = invalid argument (non-monotone seg_ptr, index >= n, rank >= segment
+ * size, ranks not two adjacent pairs), -5 = declined (the context does not fit about 0.8 of the
+ * free device memory, or 2^31 entries), -3 = HIP error; NULL is returned unless 0.
+ * lsq_rde_select: for the active segments seg[a] (each at most once) and their trial s[a], the
+ * four order statistics of r / sqrt(s[a]² + σ²) — raw != 0: of r itself — over segment seg[a] go
+ * to out[4a..4a+4), bit-identical to np.sort(x)[ranks] (±0 may differ in sign).  An MSB-first
+ * radix select on order-preserving 64-bit keys, no sort: segments of up to lsq_rde_small_max()
+ * points run one workgroup each with their keys in LDS, larger ones multi-workgroup histogram
+ * passes with the bucket decisions taken on the device; one launch sequence and one
+ * device-to-host copy per call.  A context of lsq_rde_create refuses lsq_rde_select and a
+ * segmented one lsq_rde_order_stats (-2). */
+lsq_rde* lsq_rde_create_segments(int32_t device, int64_t n, const double* r, const double* sigma,
+                                 int64_t n_seg, const int64_t* seg_ptr, const int32_t* seg_idx,
+                                 const int64_t* seg_rank, int* status);
+int lsq_rde_select(lsq_rde* c, int64_t n_act, const int32_t* seg, const double* s, int32_t raw,
+                   double* out);
+int64_t lsq_rde_small_max(void);
 
 /* Bench / profiling hooks.  lsq_profile_kernels times each iteration kernel of the operator
  * `op` (lsq_opts.op) in isolation (reps launches each, HIP events on the handle's stream):

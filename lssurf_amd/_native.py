@@ -60,6 +60,7 @@ EXPORTS = ['lsq_default_opts', 'lsq_create', 'lsq_destroy', 'lsq_last_error', 'l
            'lsq_dgroup_create', 'lsq_dgroup_rank', 'lsq_dgroup_solve', 'lsq_dgroup_iterate', 'lsq_dgroup_last_error',
            'lsq_dgroup_destroy', 'lsq_fence_selftest',
            'lsq_rde_create', 'lsq_rde_order_stats', 'lsq_rde_last_error', 'lsq_rde_destroy',
+           'lsq_rde_create_segments', 'lsq_rde_select', 'lsq_rde_small_max',
            'tri_upper_solve_csr', 'tri_upper_inv_csr', 'tri_upper_rowrss_csr', 'tri_last_error']
 
 _lib = None
@@ -135,6 +136,9 @@ def load():
         'lsq_rde_order_stats': ([P, f64, i64, P, P], ctypes.c_int),
         'lsq_rde_last_error': ([P], ctypes.c_char_p),
         'lsq_rde_destroy': ([P], None),
+        'lsq_rde_create_segments': ([i32, i64, P, P, i64, P, P, P, P], P),
+        'lsq_rde_select': ([P, i64, P, P, i32, P], ctypes.c_int),
+        'lsq_rde_small_max': ([], i64),
         'tri_upper_solve_csr': ([i32, i64, P, P, P, P, P], ctypes.c_int),
         'tri_upper_inv_csr': ([i32, i64, P, P, P, i64, ctypes.c_float, P, P, P, P], ctypes.c_int),
         'tri_upper_rowrss_csr': ([i32, i64, P, P, P, P], ctypes.c_int),

@@ -293,7 +293,8 @@ def iterate_fit(data, system, rhs, TCinv, G_data, Gc, in_TSE, timing, args, grid
             sigma_extra = calc_sigma_extra_on_grid(data.x, data.y, r_data, data.sigma, in_TSE,
                                                    sigma_extra_masks=sigma_extra_masks,
                                                    sigma_extra_max=args['sigma_extra_max'],
-                                                   spacing=args['sigma_extra_bin_spacing'])
+                                                   spacing=args['sigma_extra_bin_spacing'],
+                                                   device=args['device'])
         sigma_aug = np.sqrt(data.sigma ** 2 + sigma_extra ** 2)
         in_TSE_last = in_TSE
         in_TSE = np.abs(r_data / sigma_aug) < 3.0
