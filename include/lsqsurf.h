@@ -437,6 +437,26 @@ int lsq_profile_cg(lsq_handle* h, int32_t reps, int32_t precond, double* out8);
 int lsq_mg_info(lsq_handle* h, int64_t* out, int64_t cap);
 int lsq_mg_apply(lsq_handle* h, int32_t level, int32_t what, const double* x, double* y);
 int lsq_normal_apply(lsq_handle* h, const double* p, double* q);
+
+/* Data biases: one additive unknown b_j per bias ID on the data rows (data row i gains a 1 in the
+ * column of id[i]) with the constraint rows c_j b_j = 0 (c_j = 1 / the bias's expected size).  The
+ * library never forms these columns: CGNR eliminates them exactly, solving the reduced problem in
+ * the grid unknowns (normal operator AᵀA − A_dᵀ W Q W A_d, Q = W B D⁻¹ Bᵀ W, D_j = Σ_{i∈j} W_i² + c_j²,
+ * W = the data rows' current weight × mask), so x keeps its length.
+ * lsq_set_data_bias: call after lsq_set_matrix_stencil.  id[i] ∈ [0, nb) for data row i in the
+ * caller's row order, c[j] > 0; npts must equal the system's data rows.  nb = 0 or a null pointer
+ * clears the biases.  Returns −2 (the handle and any biases set before stay as they were) on an ID
+ * out of range, a c that is not > 0, or a wrong npts.  The biases belong to the handle's matrix: a
+ * handle takes one matrix (a second lsq_set_matrix_* returns −2 and changes nothing, the biases
+ * included), and every formation of the operator starts without biases.
+ * With biases set, lsq_solve / lsq_iterate run only as matrix-free CGNR on one GPU (method 1,
+ * precond 1, 3 or 4, interpolation grids on one (y, x) lattice); anything else returns −2 with the
+ * reason, and lsq_cg_available reports 0 with it.  lsq_normal_apply then applies the reduced
+ * operator.  lsq_spmv / lsq_spmv_rows / lsq_get_csr stay the grid operator only.
+ * lsq_get_data_bias: the nb biases that belong to the last lsq_solve's x,
+ * b_j = Σ_{i∈j} W_i² (d_i − (A_d x)_i) / D_j (0 for an ID no row carries); −2 before any solve. */
+int lsq_set_data_bias(lsq_handle* h, int64_t npts, const int32_t* id, int64_t nb, const double* c);
+int lsq_get_data_bias(lsq_handle* h, double* b);
 int lsq_sell_info(lsq_handle* h, int64_t* out8);
 
 /* ---- triangular kernels (replace the Cython kernels; R upper triangular CSR, int32 indices,

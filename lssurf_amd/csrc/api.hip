@@ -16,6 +16,10 @@ int cg_iterate(System& S, const double* h_b, int64_t iters, const lsq_opts& o, l
 void cg_profile(System& S, int reps, int precond, double* out);
 void cg_apply_normal(System& S, const double* h_p, double* h_q);
 void cg_data_colsum(System& S, const double* h_f, double* h_out);
+void bias_set(System& S, int64_t npts, const int32_t* h_id, int64_t nb, const double* h_c);
+void bias_clear(System& S);
+void bias_get(System& S, double* h_b);
+std::string bias_refusal(System& S, int method, int precond);
 int lsqr_iterate(System& S, const double* h_b, int64_t iters, const lsq_opts& o, lsq_stats* stats);
 void lsqr_profile(System& S, int reps, int op, double* out);
 void lsqr_sigma_x(System& S, double* h_E);
@@ -298,6 +302,10 @@ int lsq_solve(lsq_handle* h, const double* b, double* x_inout, const lsq_opts* o
         if (o->method != 0 && o->method != 1) return fail(S, "lsq_solve: method must be 0 (LSQR) or 1 (CGNR)");
         if (o->precond < 0 || o->precond > 5) return fail(S, "lsq_solve: precond must be 0 .. 5");
         if (o->precond == 5 && S.dist) return fail(S, "lsq_solve: precond 5 (band factor) is single-GPU");
+        if (S.bias.nb) {
+            const std::string why = lsq::bias_refusal(S, o->method, o->precond);
+            if (!why.empty()) return fail(S, "lsq_solve: " + why);
+        }
         if (o->precond == 4 && (o->method != 1 || (!S.dist && !lsq::cg_available(S, 4))))
             return fail(S, "lsq_solve: precond 4 (multigrid) runs CGNR (method 1) on structured systems: " +
                                (o->method != 1 ? std::string("method is not 1") : S.cg_ok ? S.mg_why : S.cg_why));
@@ -331,6 +339,10 @@ int lsq_iterate(lsq_handle* h, const double* b, int64_t iters, const lsq_opts* o
         lsq_opts d;
         lsq_default_opts(&d);
         if (!o) o = &d;
+        if (S.bias.nb) {
+            const std::string why = lsq::bias_refusal(S, o->method, o->precond);
+            if (!why.empty()) return fail(S, "lsq_iterate: " + why);
+        }
         if (o->precond == 4 && (o->method != 1 || (!S.dist && !lsq::cg_available(S, 4))))
             return fail(S, "lsq_iterate: precond 4 (multigrid) runs CGNR (method 1) on structured systems: " +
                                (o->method != 1 ? std::string("method is not 1") : S.cg_ok ? S.mg_why : S.cg_why));
@@ -352,6 +364,13 @@ int lsq_cg_available(lsq_handle* h, int32_t precond) {
         if (precond != 1 && precond != 3 && precond != 4) {
             S.err = "CGNR runs with precond 1 (Jacobi), 3 (block-Jacobi) or 4 (multigrid)";
             return 0;
+        }
+        if (S.bias.nb) {   // biases set: only the matrix-free CGNR operator carries them
+            const std::string why = lsq::bias_refusal(S, 1, precond);
+            if (!why.empty()) {
+                S.err = why;
+                return 0;
+            }
         }
         if (lsq::cg_available(S, precond)) return 1;
         S.err = !S.cg_ok ? (S.cg_why.empty() ? "not a structured single-GPU system" : S.cg_why) : S.mg_why;
@@ -393,6 +412,27 @@ int lsq_normal_apply(lsq_handle* h, const double* p, double* q) {
         if (!p || !q) return fail(S, "lsq_normal_apply: null vector");
         if (!lsq::cg_available(S, 1)) return fail(S, "lsq_normal_apply: no normal-stencil operator: " + S.cg_why);
         lsq::cg_apply_normal(S, p, q);
+        return 0;
+    });
+}
+
+int lsq_set_data_bias(lsq_handle* h, int64_t npts, const int32_t* id, int64_t nb, const double* c) {
+    return guarded(h, [&](lsq::System& S) {
+        if (!S.G.rp.p) return fail(S, "lsq_set_data_bias: no matrix");
+        if (nb < 0 || npts < 0) return fail(S, "lsq_set_data_bias: bad sizes");
+        if (nb == 0 || !id || !c) {
+            lsq::bias_clear(S);
+            return 0;
+        }
+        lsq::bias_set(S, npts, id, nb, c);
+        return 0;
+    });
+}
+
+int lsq_get_data_bias(lsq_handle* h, double* b) {
+    return guarded(h, [&](lsq::System& S) {
+        if (!b) return fail(S, "lsq_get_data_bias: null output");
+        lsq::bias_get(S, b);
         return 0;
     });
 }

@@ -757,6 +757,7 @@ void finish_formation(System& S) {
     S.nblk = 0;   // column blocks refer to the previous column numbering
     S.blk_user = false;
     S.blk_valid = false;
+    S.bias = BiasData{};   // data biases index the previous formation's sorted points
     HIP_CHECK(hipStreamSynchronize(st));
 }
 

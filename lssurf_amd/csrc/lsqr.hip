@@ -27,6 +27,7 @@ namespace lsq {
 namespace {
 
 constexpr int NPART = 2048;   // partial-sum slots per reduction (fixed grid => deterministic)
+constexpr int BIAS_NPART = 64;   // further slots behind them: the data-bias elimination's partials (bias.inc)
 
 // ---- SELL-64 row kernel body: one lane = one row, 4 entries in flight per step -------------
 __device__ __forceinline__ double sell_row_dot(const int32_t* __restrict__ ci, const double* __restrict__ val,
@@ -436,10 +437,10 @@ void ensure_workspace(System& S) {
         S.tt.alloc(n);
     }
     if (!S.part_u.p) {
-        S.part_u.alloc(NPART);
+        S.part_u.alloc(NPART + BIAS_NPART);
         S.part_v.alloc(NPART);
         S.part_w.alloc(NPART);
-        S.part_b.alloc(NPART);
+        S.part_b.alloc(NPART + BIAS_NPART);
         S.st.alloc(1);
     }
 }

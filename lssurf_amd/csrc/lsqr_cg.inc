@@ -2000,7 +2000,7 @@ void cg_workspace(System& S) {
     const int npg = cg_grid_normal(S) + (S.cgh.colmode ? S.cgh.nedge : 0) + S.cg_nvb;
     if (S.cg_part_g.n != npg) S.cg_part_g.alloc(npg);
     if (!S.cg_part_r.p) S.cg_part_r.alloc(NPART);
-    if (!S.cg_part_t.p) S.cg_part_t.alloc(NPART);
+    if (!S.cg_part_t.p) S.cg_part_t.alloc(NPART + BIAS_NPART);   // the data rows' partials, then the biases'
     if (!S.cst.p) S.cst.alloc(1);
     if (!S.side) {
         HIP_CHECK(hipStreamCreateWithFlags(&S.side, hipStreamNonBlocking));
@@ -2094,19 +2094,33 @@ void cg_launch_precond(System& S, const CgGrids& g, int precond) {
 // before the normal kernel), column mode reads the p the normal kernel wrote
 bool cg_use_dmf(const System& S) { return S.cgh.colmode && S.dmf.ok; }
 
+#include "bias.inc"
+
 // the data rows' row scales in the matrix-free point order (per solve)
 void cg_dmf_prepare(System& S) {
     if (!cg_use_dmf(S)) return;
     hipLaunchKernelGGL(k_dmf_rs, dim3(grid_for(S.dmf.npts)), dim3(BLOCK), 0, S.stream, S.dmf.npts, S.dmf_perm.p,
                        S.rs.p, reinterpret_cast<double4*>(S.dmf_pt.p));
     KERNEL_CHECK();
+    if (bias_active(S)) bias_prepare(S);
+}
+
+// the data rows' partials of pᵀNp: Σt² per workgroup, then (biases set) −Σ_j s_j²/D_j
+int cg_nt(const System& S, const CgGrids& g) {
+    return S.cgh.colmode ? g.gD + (bias_active(S) ? S.bias.nbk : 0) : 0;
+}
+
+// biases set: td ← W(I − Q)W A_d p between Ad·p and q += Adᵀ td (bias.inc)
+void cg_launch_bias(System& S, const CgGrids& g) {
+    if (bias_active(S)) bias_launch_step(S, S.cst.p, S.cg_t.p, S.cg_part_t.p + g.gD);
 }
 
 void cg_launch_data(System& S, const CgGrids& g, const double* pold, const double* pnew) {
-    if (cg_use_dmf(S))
+    if (cg_use_dmf(S)) {
         hipLaunchKernelGGL(k_cg_dmf_ad, dim3(g.gD), dim3(BLOCK), 0, S.stream, S.cst.p, S.dmf,
                            reinterpret_cast<const double4*>(S.dmf_pt.p), pnew, S.cg_t.p, S.cg_part_t.p);
-    else if (S.cgh.colmode)
+        cg_launch_bias(S, g);
+    } else if (S.cgh.colmode)
         hipLaunchKernelGGL(k_cg_data, dim3(g.gD), dim3(BLOCK), 0, S.stream, S.cst.p, S.mfh.npts, S.Ad.nslices,
                            S.Ad.sp.p, S.Ad.ci.p, S.Ad.val.p, pnew, nullptr, S.cg_t.p, S.cg_part_t.p);
     else
@@ -2184,7 +2198,7 @@ void cg_launch_normal(System& S, const CgGrids& g, const double* pold, double* p
 
 void cg_launch_alpha(System& S, const CgGrids& g) {
     hipLaunchKernelGGL(k_cg_alpha, dim3(1), dim3(BLOCK), 0, S.stream, S.cst.p, S.cg_part_g.p,
-                       g.gN + (S.cgh.colmode ? S.cgh.nedge : 0) + S.cg_nvb, S.cg_part_t.p, S.cgh.colmode ? g.gD : 0,
+                       g.gN + (S.cgh.colmode ? S.cgh.nedge : 0) + S.cg_nvb, S.cg_part_t.p, cg_nt(S, g),
                        S.dist ? S.gsum.p : nullptr);
 }
 
@@ -2201,13 +2215,13 @@ void cg_launch_iteration(System& S, const CgGrids& g, int ph, int precond) {
         hipLaunchKernelGGL(k_cg_ad_xedge<8>, dim3(g.gD + S.cgh.nedge), dim3(BLOCK), 0, S.stream, S.cst.p, S.dmf,
                            reinterpret_cast<const double4*>(S.dmf_pt.p), pnew, S.cg_t.p, S.cg_part_t.p, g.gD, S.cgd.p,
                            S.cg_coef.p, S.cg_q.p, S.cg_part_g.p + g.gN);
+        cg_launch_bias(S, g);
         // α in the node gather's workgroup 0 (LSQ_CG_FUSE_ALPHA=0: its own launch)
         static const bool fuse_env = !getenv("LSQ_CG_FUSE_ALPHA") || atoi(getenv("LSQ_CG_FUSE_ALPHA")) != 0;
         const char* rw = getenv("LSQ_CG_ATQ_RW");
         if (fuse_env && !S.dist && !(rw && rw[0] == '1')) {
             cg_launch_dmf_atq(S, S.cst.p, S.cg_t.p, S.cg_q.p, S.cst.p, S.cg_part_g.p,
-                              g.gN + (S.cgh.colmode ? S.cgh.nedge : 0) + S.cg_nvb, S.cg_part_t.p,
-                              S.cgh.colmode ? g.gD : 0);
+                              g.gN + (S.cgh.colmode ? S.cgh.nedge : 0) + S.cg_nvb, S.cg_part_t.p, cg_nt(S, g));
             cg_launch_precond(S, g, precond);
             hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(BLOCK), 0, S.stream, S.cst.p, S.cg_part_r.p, g.gB, 0, nullptr);
             return;
@@ -2286,9 +2300,13 @@ void cg_init(System& S, const double* h_b, const double* h_x0, const lsq_opts& o
         hipLaunchKernelGGL(k_cg_init_dmf, dim3(gi), dim3(BLOCK), 0, st, S.dmf.npts, S.dmf_perm.p,
                            reinterpret_cast<const double4*>(S.dmf_pt.p), dbp, S.cg_t.p, S.part_u.p);
         KERNEL_CHECK();
+        // biases set: td ← W(I − Q)W b and ‖r0‖² = bᵀW(I − Q)W b, the reduced problem's
+        const int nbk = bias_active(S) ? S.bias.nbk : 0;
+        if (nbk) bias_launch_step(S, S.cst.p, S.cg_t.p, S.part_u.p + gi);
         cg_launch_dmf_atq(S, S.cst.p, S.cg_t.p, S.cg_s.p);
         KERNEL_CHECK();
-        hipLaunchKernelGGL(k_cg_init, dim3(1), dim3(BLOCK), 0, st, S.cst.p, S.part_u.p, gi, S.part_u.p, gi, nullptr);
+        hipLaunchKernelGGL(k_cg_init, dim3(1), dim3(BLOCK), 0, st, S.cst.p, S.part_u.p, gi + nbk, S.part_u.p, gi + nbk,
+                           nullptr);
     } else {
         // u = W b − A x0 over all rows (Σu² = ‖r0‖²), then s0 = Aᵀu (raw, full space)
         hipLaunchKernelGGL(k_mf_init_u_for(S), dim3(lg.gD + lg.gS), dim3(BLOCK), 0, st, lg.gD, S.mfh.npts, S.Ad.nslices,
@@ -2298,8 +2316,27 @@ void cg_init(System& S, const double* h_b, const double* h_x0, const lsq_opts& o
         hipLaunchKernelGGL(k_mf_spmtv_for(S), dim3(lg.gM), dim3(BLOCK), 0, st, S.st.p, S.ATd.rp.p, S.ATd.ci.p,
                            S.ATd.val.p, S.mfd.p, S.u.p, S.rs.p, S.csf.p, S.cg_q.p, S.cg_s.p, S.zv.p, S.part_v.p, 1);
         KERNEL_CHECK();
-        hipLaunchKernelGGL(k_cg_init, dim3(1), dim3(BLOCK), 0, st, S.cst.p, S.part_u.p, lg.gD + lg.gS, S.part_b.p,
-                           lg.gD + lg.gS, nullptr);
+        const int nbk = bias_active(S) ? S.bias.nbk : 0;
+        if (nbk) {
+            // the reduced problem's u_d = (I − Q) W (b − A_d x0): with e = W²(b − A_d x0) per sorted point
+            // and s_j = Σ_{i∈j} e_i, s0 −= A_dᵀ(W² s/D), ‖r0‖² −= Σ s_j²/D_j; the same on W b for ‖b‖
+            const BiasData& B = S.bias;
+            const int nu = lg.gD + lg.gS, ge = grid_for(B.npts);
+            hipLaunchKernelGGL(k_bias_resid, dim3(ge), dim3(BLOCK), 0, st, B.npts, S.dmf_perm.p, B.w2.p, dbp, nullptr,
+                               S.cg_t.p);
+            bias_launch_reduce(S, nullptr, S.cg_t.p, S.part_b.p + nu);
+            hipLaunchKernelGGL(k_cg_dmf_ad, dim3(g.gD), dim3(BLOCK), 0, st, S.cst.p, S.dmf,
+                               reinterpret_cast<const double4*>(S.dmf_pt.p), S.cg_x.p, S.cg_t.p, S.cg_part_t.p);
+            hipLaunchKernelGGL(k_bias_resid, dim3(ge), dim3(BLOCK), 0, st, B.npts, S.dmf_perm.p, B.w2.p, dbp, S.cg_t.p,
+                               S.cg_t.p);
+            bias_launch_reduce(S, nullptr, S.cg_t.p, S.part_u.p + nu);
+            hipLaunchKernelGGL(k_bias_apply, dim3(ge), dim3(BLOCK), 0, st, nullptr, B.npts, B.rank_pt.p, B.w2.p, B.sD.p,
+                               S.cg_t.p, 1);
+            cg_launch_dmf_atq(S, S.cst.p, S.cg_t.p, S.cg_s.p);
+            KERNEL_CHECK();
+        }
+        hipLaunchKernelGGL(k_cg_init, dim3(1), dim3(BLOCK), 0, st, S.cst.p, S.part_u.p, lg.gD + lg.gS + nbk, S.part_b.p,
+                           lg.gD + lg.gS + nbk, nullptr);
     }
     tr.mark(st, "s0 = A'(Wb-Ax0)");
     if (precond == 4) {   // multigrid set-up for these row weights (uses q as scratch)
@@ -2360,6 +2397,7 @@ void cg_kernel_bytes(const System& S, int precond, double out[3]) {
         // point subscripts + scale and td again, q RMW at the data columns)
         const double ncell = (double)(S.dmf.S0 - 1) * (double)(S.dmf.S1 - 1);
         out[0] = 40.0 * md + 8.0 * nd + 4.0 * ncell + 40.0 * md + 16.0 * nd;
+        if (bias_active(S)) out[0] += bias_step_bytes(S);
         out[1] = 32.0 * nf;
     } else if (S.cgh.colmode) {
         // data = Ad·p (12 B/entry, p gathers, t) + ATd·t (entries, row pointers, t gathers, q RMW)
@@ -2399,6 +2437,8 @@ void cg_fill_stats(const CgState& h, lsq_stats* s) {
 
 }  // namespace
 
+void bias_values(System& S, const double* dbp);
+
 bool cg_available(System& S, int precond) {
     if (precond != 1 && precond != 3 && precond != 4) return false;
     return cg_prepare(S, precond) && (precond != 4 || S.mg);
@@ -2436,6 +2476,7 @@ int cg_solve(System& S, const double* h_b, double* h_x, const lsq_opts& o, lsq_s
     KERNEL_CHECK();
     dx.download(h_x, n, S.stream);
     HIP_CHECK(hipStreamSynchronize(S.stream));
+    if (S.bias.nb) bias_values(S, S.rhs.p);   // the biases that belong to this x
     float ms = 0.f;
     HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
     (void)hipEventDestroy(e0);
@@ -2634,4 +2675,142 @@ void cg_apply_normal(System& S, const double* h_p, double* h_q) {
     S.cg_q.download(h_q, nf, S.stream);
     HIP_CHECK(hipStreamSynchronize(S.stream));
     S.cg_ready = false;
+}
+
+// ---- data biases (bias.inc): set, clear, read back ---------------------------------------------
+void bias_clear(System& S) {
+    if (!S.bias.on && !S.bias.idx.p) return;
+    graph_cache_drop(&S);   // captured iterations hold the step's launches
+    S.bias = BiasData{};
+    S.cg_ready = false;
+}
+
+// id: the data rows' bias IDs in the caller's row order; c: 1 / E_bias per ID
+void bias_set(System& S, int64_t npts, const int32_t* h_id, int64_t nb, const double* h_c) {
+    if (!S.mf || S.dist) throw std::invalid_argument("lsq_set_data_bias: needs a single-GPU structured system (lsq_set_matrix_stencil)");
+    if (npts != S.mfh.npts) throw std::invalid_argument("lsq_set_data_bias: npts differs from the system's data rows");
+    if (nb >= (int64_t)INT32_MAX) throw std::invalid_argument("lsq_set_data_bias: too many bias IDs");
+    if (!S.dmf.ok || S.dmf.npts != npts)
+        throw std::invalid_argument("lsq_set_data_bias: needs matrix-free data rows (interpolation grids on one (y, x) lattice)");
+    // validation on the device
+    DBuf<int32_t> did(std::max<int64_t>(npts, 1));
+    DBuf<double> dc(nb);
+    DBuf<int> flag(1);
+    did.upload(h_id, npts, S.stream);
+    dc.upload(h_c, nb, S.stream);
+    flag.zero(S.stream);
+    hipLaunchKernelGGL(k_bias_validate, dim3(grid_for(std::max(npts, nb))), dim3(BLOCK), 0, S.stream, npts, did.p, nb,
+                       dc.p, flag.p);
+    KERNEL_CHECK();
+    int hf = 0;
+    std::vector<int32_t> perm(npts);
+    flag.download(&hf, 1, S.stream);
+    S.dmf_perm.download(perm.data(), npts, S.stream);
+    HIP_CHECK(hipStreamSynchronize(S.stream));
+    if (hf & 1) throw std::invalid_argument("lsq_set_data_bias: a bias ID lies outside [0, nb)");
+    if (hf & 2) throw std::invalid_argument("lsq_set_data_bias: every c must be > 0");
+    bias_clear(S);
+    graph_cache_drop(&S);   // captured iterations hold no elimination step yet
+    S.cg_ready = false;
+    // ranks: the IDs that carry points, in ID order; the sorted points indexed stably by rank
+    std::vector<int32_t> cnt(nb + 1, 0), rank_of(nb, -1), rank_id;
+    for (int64_t i = 0; i < npts; ++i) ++cnt[h_id[i]];
+    for (int64_t j = 0; j < nb; ++j)
+        if (cnt[j]) {
+            rank_of[j] = (int32_t)rank_id.size();
+            rank_id.push_back((int32_t)j);
+        }
+    const int64_t ns = (int64_t)rank_id.size();
+    std::vector<int32_t> seg(ns + 1, 0), pos(std::max<int64_t>(ns, 1)), idx(std::max<int64_t>(npts, 1)),
+        brank(std::max<int64_t>(npts, 1)), rank_pt(std::max<int64_t>(npts, 1));
+    std::vector<double> c2(std::max<int64_t>(ns, 1));
+    for (int64_t r = 0; r < ns; ++r) {
+        seg[r + 1] = seg[r] + cnt[rank_id[r]];
+        pos[r] = seg[r];
+        c2[r] = h_c[rank_id[r]] * h_c[rank_id[r]];
+    }
+    for (int64_t i = 0; i < npts; ++i) {
+        const int32_t r = rank_of[h_id[perm[i]]];
+        rank_pt[i] = r;
+        const int32_t k = pos[r]++;
+        idx[k] = (int32_t)i;
+        brank[k] = r;
+    }
+    const int64_t nchunk = (npts + BIAS_CHUNK - 1) / BIAS_CHUNK;
+    std::vector<int32_t> sbase(std::max<int64_t>(nchunk, 1));
+    int64_t nslots = 0;
+    for (int64_t c = 0; c < nchunk; ++c) {
+        const int32_t ra = brank[c * BIAS_CHUNK], rb = brank[std::min(npts, (c + 1) * BIAS_CHUNK) - 1];
+        sbase[c] = (int32_t)(nslots - ra);
+        nslots += rb - ra + 1;
+    }
+    std::vector<int32_t> long_rank, long_of(std::max<int64_t>(ns, 1), -1);
+    for (int64_t r = 0; r < ns; ++r)
+        if ((seg[r + 1] - 1) / BIAS_CHUNK - seg[r] / BIAS_CHUNK + 1 > BIAS_LONG) {
+            long_of[r] = (int32_t)long_rank.size();
+            long_rank.push_back((int32_t)r);
+        }
+    BiasData& B = S.bias;
+    B.nb = nb; B.ns = ns; B.npts = npts; B.nchunk = nchunk; B.nslots = nslots;
+    B.nlong = (int64_t)long_rank.size();
+    B.lsum.alloc(std::max<int64_t>(B.nlong, 1));
+    B.nbk = grid_for(ns, BLOCK, BIAS_NPART);
+    auto up = [&](DBuf<int32_t>& d, const std::vector<int32_t>& h) {
+        d.alloc((int64_t)h.size());
+        d.upload(h.data(), (int64_t)h.size(), S.stream);
+    };
+    up(B.idx, idx); up(B.brank, brank); up(B.rank_pt, rank_pt); up(B.seg, seg); up(B.sbase, sbase);
+    up(B.long_of, long_of);
+    long_rank.resize(std::max<size_t>(long_rank.size(), 1));
+    up(B.long_rank, long_rank);
+    rank_id.resize(std::max<int64_t>(ns, 1));
+    up(B.rank_id, rank_id);
+    B.c2.alloc((int64_t)c2.size());
+    B.c2.upload(c2.data(), (int64_t)c2.size(), S.stream);
+    B.w2.alloc(std::max<int64_t>(npts, 1));
+    B.D.alloc(std::max<int64_t>(ns, 1));
+    B.sD.alloc(std::max<int64_t>(ns, 1));
+    B.slots.alloc(std::max<int64_t>(nslots, 1));
+    B.bval.alloc(nb);
+    HIP_CHECK(hipStreamSynchronize(S.stream));
+    B.on = npts > 0 && ns > 0;   // no data rows: every bias is 0, the operator is unchanged
+}
+
+// the biases of the x in S.cg_x (full space) for the right-hand side dbp: b_j = Σ W²(d − A_d x) / D_j
+void bias_values(System& S, const double* dbp) {
+    BiasData& B = S.bias;
+    B.bval.zero(S.stream);
+    if (bias_active(S)) {
+        const CgGrids g = cg_grids(S, 1);
+        DBuf<CgState> st(1);
+        st.zero(S.stream);
+        hipLaunchKernelGGL(k_cg_dmf_ad, dim3(g.gD), dim3(BLOCK), 0, S.stream, st.p, S.dmf,
+                           reinterpret_cast<const double4*>(S.dmf_pt.p), S.cg_x.p, S.cg_t.p, S.cg_part_t.p);
+        hipLaunchKernelGGL(k_bias_resid, dim3(grid_for(B.npts)), dim3(BLOCK), 0, S.stream, B.npts, S.dmf_perm.p, B.w2.p,
+                           dbp, S.cg_t.p, S.cg_t.p);
+        bias_launch_reduce(S, nullptr, S.cg_t.p, nullptr);
+        hipLaunchKernelGGL(k_bias_scatter, dim3(grid_for(B.ns)), dim3(BLOCK), 0, S.stream, B.ns, B.rank_id.p, B.sD.p,
+                           B.bval.p);
+        KERNEL_CHECK();
+        HIP_CHECK(hipStreamSynchronize(S.stream));
+    }
+    B.solved = true;
+}
+
+void bias_get(System& S, double* h_b) {
+    if (!S.bias.nb) throw std::invalid_argument("lsq_get_data_bias: no biases set");
+    if (!S.bias.solved) throw std::invalid_argument("lsq_get_data_bias: no lsq_solve since the biases were set");
+    S.bias.bval.download(h_b, S.bias.nb, S.stream);
+    HIP_CHECK(hipStreamSynchronize(S.stream));
+}
+
+// why a solve with biases set cannot run (empty: it can)
+std::string bias_refusal(System& S, int method, int precond) {
+    if (!S.bias.nb) return "";
+    if (S.dist) return "data biases run on single-GPU handles only";
+    if (method != 1) return "data biases need CGNR (method 1)";
+    if (precond != 1 && precond != 3 && precond != 4) return "data biases run with precond 1, 3 or 4";
+    if (!cg_available(S, precond)) return "data biases need the structured CGNR operator: " + (S.cg_ok ? S.mg_why : S.cg_why);
+    if (!cg_use_dmf(S)) return "data biases need the matrix-free column-mode CGNR data rows (tile mode is not covered)";
+    return "";
 }

@@ -304,6 +304,36 @@ struct CgState {
     double anorm_seed;   // lsq_opts.anorm0: the stopping rule's ‖A‖ is max(seed, sqrt(anorm2))
 };
 
+// Data biases eliminated from the CGNR normal equations (bias.inc): one additive unknown per bias
+// ID on the data rows, constrained by b_j·c_j = 0.  IDs that carry points are numbered densely
+// ("ranks", in ID order); the sorted points (dmf_perm order) are indexed stably by rank, and that
+// index is cut into fixed chunks of BIAS_CHUNK entries, one wave each.  A chunk owns one partial-sum
+// slot per rank it touches (slot = sbase[chunk] + rank), so every segmented sum is a fixed set of
+// plain stores followed by a fixed-order sum per rank (a thread per rank, a wave per rank over many
+// chunks): bitwise reproducible, no atomics.
+struct BiasData {
+    bool on = false;
+    bool solved = false;            // bval belongs to the last lsq_solve's x
+    int64_t nb = 0, ns = 0, npts = 0, nchunk = 0, nslots = 0;   // IDs, ranks, points, chunks, slots
+    int64_t nlong = 0;              // ranks over more than BIAS_LONG chunks (a wave each: k_bias_long)
+    DBuf<int32_t> long_rank;        // their ranks
+    DBuf<int32_t> long_of;          // rank -> position in long_rank, or −1
+    DBuf<double> lsum;              // their slot sums
+    int nbk = 0;                    // workgroups (= partials) of the per-rank sum
+    DBuf<int32_t> idx;              // rank-sorted position -> sorted point
+    DBuf<int32_t> brank;            // rank-sorted position -> rank
+    DBuf<int32_t> rank_pt;          // sorted point -> rank
+    DBuf<int32_t> seg;              // rank -> first rank-sorted position (ns + 1)
+    DBuf<int32_t> sbase;            // chunk -> first slot − first rank
+    DBuf<int32_t> rank_id;          // rank -> bias ID
+    DBuf<double> c2;                // rank -> c²
+    DBuf<double> w2;                // sorted point -> row scale² (per solve)
+    DBuf<double> D;                 // rank -> Σ w² + c² (per solve)
+    DBuf<double> sD;                // rank -> s / D of the last reduction
+    DBuf<double> slots;
+    DBuf<double> bval;              // ID -> bias of the last solve
+};
+
 struct System {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -431,6 +461,7 @@ struct System {
     DBuf<double> dmf_pt;            // per sorted point: f_y, f_x, f_t, row scale (double4)
     DBuf<int32_t> dmf_perm, dmf_cell;   // sorted point -> data row; (y, x) cell -> first sorted point
     std::string cg_why;            // why not (when !cg_ok)
+    BiasData bias;                  // eliminated data biases (lsq_set_data_bias; bias.inc)
     CgDesc cgh{};
     DBuf<CgDesc> cgd;
     DBuf<double> cg_coef, cg_coefc;  // class-row tables: offset-major (tile mode), group × t (column mode)

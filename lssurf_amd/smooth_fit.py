@@ -13,9 +13,11 @@ valid_data, TOC, R, RMS, timing, E_RMS, dzdt_lags; ``return_fit_objects`` early 
 * everything else (editing, sigma_extra, convergence tests, parse_model) keeps the reference's
   logic on the host.
 
-Options that add columns/rows outside the fd_grid model (biases, sensor grids, jitter,
-priors, lagrangian grids, averaging masks) are outside lssurf_amd's scope and raise
-NotImplementedError instead of silently changing the fit.
+Options that add columns/rows outside the fd_grid model (sensor grids, jitter, priors,
+lagrangian grids) are outside lssurf_amd's scope and raise NotImplementedError instead of
+silently changing the fit.  Data biases (bias_params) run when the solver key lsq_bias says how:
+'eliminate' (the device eliminates them inside CGNR, lsq_set_data_bias), 'columns' (ordinary
+columns of a generic system) or 'auto'.
 """
 from time import ctime, time
 
@@ -23,6 +25,7 @@ import warnings
 import numpy as np
 
 from . import containers as pc
+from .bias_functions import assign_bias_ID, bias_expected, edit_by_bias, parse_biases, setup_bias_fit
 from .calc_sigma_extra import RDE, calc_sigma_extra, calc_sigma_extra_on_grid
 from .constraint_functions import build_reference_epoch_matrix, node_column_blocks, \
     node_column_blocks_affine, reference_epoch_keep_cols, \
@@ -51,9 +54,11 @@ DEFAULTS = {'reference_epoch': 0, 'W_ctr': 1e4, 'return_fit_objects': False, 'ma
             # the tolerance documented in DESIGN.md §Parity)
             'device': 0, 'lsq_atol': 1e-12, 'lsq_btol': 1e-12, 'lsq_conlim': 1e12, 'lsq_maxit': 0,
             'lsq_precond': 'auto', 'lsq_dense_max': 16384, 'lsq_warm_start': True, 'lsq_method': 'auto',
-            'lsq_reuse_anorm': True, 'lsq_E_method': 'auto', 'n_gpus': 1, 'devices': None}
+            'lsq_reuse_anorm': True, 'lsq_E_method': 'auto', 'n_gpus': 1, 'devices': None,
+            # data biases (bias_params): None refuses them; 'eliminate', 'columns' or 'auto'
+            'lsq_bias': None}
 
-OUT_OF_SCOPE = ('bias_params', 'sensor_grid_bias_params', 'prior_args', 'prior_edge_args', 'lagrangian_coords',
+OUT_OF_SCOPE = ('sensor_grid_bias_params', 'prior_args', 'prior_edge_args', 'lagrangian_coords',
                 'constraint_scaling_maps', 'mask_file', 'bias_edit_vals')
 
 
@@ -61,7 +66,10 @@ class FitSystem:
     """The device-resident smooth_fit system: G = [G_data; Gc] (unweighted COO -> device CSR),
     Ip_c as a column map; rows re-weighted / re-selected per outer iteration."""
 
-    def __init__(self, G_data, Gc, keep_cols, n_full, device=0, structured=True, grids=None):
+    def __init__(self, G_data, Gc, keep_cols, n_full, device=0, structured=True, grids=None, bias=None):
+        """bias = (ids, c): eliminated data biases (LSQSolver.set_data_bias) — G_data and Gc are then
+        the grid-only operators, the caller's row weights and rhs may carry further (bias
+        constraint) rows behind them, and the biases take the columns after n_full in expand()."""
         self.n_data, self.n_con = int(G_data.N_eq), int(Gc.N_eq)
         self.keep_cols = keep_cols
         self.n_full = int(n_full)
@@ -98,6 +106,21 @@ class FitSystem:
         self._mg = None            # multigrid (precond 4) availability, probed on first use
         self.mg_build_s = 0.0
         self.stats = None
+        self.bias_ids, self.bias_vals = None, None
+        if bias is not None:
+            # only matrix-free CGNR carries the eliminated biases: never the dense preconditioner
+            # (LSQR), whatever the size.  'auto' then takes the node-block preconditioner: the multigrid
+            # levels are built from the unprojected operator and cost 6–21× the iterations at C4 where
+            # block-Jacobi costs 1.6–2× (profiles/bias_c4.json)
+            self.dense_ok = False
+            try:
+                ids, c = bias
+                self.bias_ids = np.asarray(ids).astype(np.int32)
+                self.solver.set_data_bias(self.bias_ids, c)
+                self.bias_vals = np.zeros(np.size(c))
+            except Exception:
+                self.solver.close()
+                raise
 
     @property
     def blocks(self):
@@ -134,17 +157,29 @@ class FitSystem:
             self._mask[:self.n_data] = dk
             self.solver.set_row_mask(self._mask)
             self._keep_last = dk.copy()
+        if self.bias_ids is not None:   # the device rows are a prefix of the caller's rows
+            rhs = rhs[:self.n_data + self.n_con]
         x, self.stats = self.solver.solve(rhs, x0=x0, b_rows=getattr(self, 'b_rows', 0), **opts)
+        if self.bias_ids is not None:
+            self.bias_vals = self.solver.data_bias()
         return x
 
     def expand(self, x):
-        m0 = np.zeros(self.n_full)
+        if self.bias_ids is not None:   # the biases of the last solve, in the columns after the grids
+            m0 = np.zeros(self.n_full + self.bias_vals.size)
+            m0[self.n_full:] = self.bias_vals
+        else:
+            m0 = np.zeros(self.n_full)
         m0[self.keep_cols] = x
         return m0
 
     def data_forward(self, x):
-        """G_data · (Ip_c x), bit-identical to scipy's csr matvec of the reference."""
-        return self.solver.spmv_rows(x, 0, self.n_data)
+        """G_data · (Ip_c x), bit-identical to scipy's csr matvec of the reference (eliminated
+        biases: plus the last solve's bias of each row's ID)."""
+        y = self.solver.spmv_rows(x, 0, self.n_data)
+        if self.bias_ids is not None:
+            y += self.bias_vals[self.bias_ids]
+        return y
 
     def rows_sumsq(self, x, ranges):
         """Per (first, count) row range of [G_data; Gc]: (Σ (w·G x)², Σ (G x)²), x compact."""
@@ -203,9 +238,12 @@ def _anorm_seed_ok(precond, weight, in_TSE, prev):
     return m.shape == prev[1].shape and int(np.count_nonzero(m != prev[1])) <= 0.01 * max(m.size, 1)
 
 
-def iterate_fit(data, system, rhs, TCinv, G_data, Gc, in_TSE, timing, args, grids, sigma_extra_masks=None):
+def iterate_fit(data, system, rhs, TCinv, G_data, Gc, in_TSE, timing, args, grids, sigma_extra_masks=None,
+                bias_model=None):
     """Outer editing loop (smooth_fit.py:100-210) around the device solve.  TCinv: the diagonal of
     the reference's TCinv (1/σ per row of [G_data; Gc])."""
+    if bias_model:   # the IDs edited before the fit keep their data out (smooth_fit.py:106)
+        edit_by_bias(data, np.zeros(Gc.col_N), in_TSE, -1, bias_model, args)
     in_TSE_original = np.zeros(data.shape, dtype=bool)
     in_TSE_original[in_TSE] = True
     N_editable = np.sum(data.editable) if 'editable' in data.fields else data.size
@@ -243,7 +281,7 @@ def iterate_fit(data, system, rhs, TCinv, G_data, Gc, in_TSE, timing, args, grid
         x0 = x if (args['lsq_warm_start'] and x is not None) else None
         dense_ok = getattr(system, 'dense_ok', True)
         mg = args['lsq_precond'] == 'auto' and (system.keep_cols.size > args['lsq_dense_max'] or not dense_ok) and \
-            system.multigrid_available(weight)
+            getattr(system, 'bias_ids', None) is None and system.multigrid_available(weight)
         if mg and 'mg_build' not in timing:
             timing['mg_build'] = system.mg_build_s
         opts = _solve_opts(args, system.keep_cols.size, system.has_blocks, mg, dense_ok)
@@ -299,6 +337,8 @@ def iterate_fit(data, system, rhs, TCinv, G_data, Gc, in_TSE, timing, args, grid
         in_TSE_last = in_TSE
         in_TSE = np.abs(r_data / sigma_aug) < 3.0
         bias_editing_changed = False
+        if bias_model:
+            bias_editing_changed = edit_by_bias(data, system.expand(x), in_TSE, iteration, bias_model, args)
         if 'editable' in data.fields:
             in_TSE[data.editable == 0] = in_TSE_original[data.editable == 0]
         if args['DEM_tol'] is not None:
@@ -491,6 +531,32 @@ def parse_model(m, m0, data, R, RMS, G_data, averaging_ops, Gc, Ec, grids, args,
                           np.sqrt(sums['notide_scaled'][cols].reshape(shape) / m[ff].count)})
 
 
+def _bias_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, bias_model, mode, grids, device, args):
+    """The device system of a fit with data biases.  'eliminate': the grid-only operators on the
+    device plus lsq_set_data_bias (the bias constraint rows are the last rows of Gc, so the device
+    rows are a prefix of the host rows); 'columns': the biases as ordinary columns of a generic
+    (COO-formed) system; 'auto': 'columns' when the grid unknowns (the eliminating system's columns)
+    are few enough for the dense preconditioner, when the options ask for what only 'columns' runs
+    (LSQR, the dense preconditioner) or when the device cannot eliminate (no matrix-free data rows),
+    else 'eliminate'."""
+    n_grid = G_grid.col_N if G_grid is not None else None
+    n_bias = int(G_data.col_N) - int(n_grid) if n_grid is not None else 0
+    if mode == 'auto' and (describe(G_grid, Gc_grid, with_fields=True) is None or
+                           np.count_nonzero(keep_cols < n_grid) <= args['lsq_dense_max'] or
+                           args['lsq_method'] == 'lsqr' or args['lsq_precond'] == 2):
+        mode = 'columns'
+    if mode != 'columns':
+        ids = np.asarray(data.bias_ID).astype(np.int32)
+        c = 1. / bias_expected(bias_model, n_bias)
+        try:
+            return FitSystem(G_grid, Gc_grid, keep_cols[keep_cols < n_grid], n_grid, device=device, grids=grids,
+                             bias=(ids, c))
+        except NativeError:
+            if mode == 'eliminate':
+                raise
+    return FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=device, grids=grids)
+
+
 def smooth_fit(**kwargs):
     required = ('data', 'W', 'ctr', 'spacing', 'E_RMS')
     args = dict(DEFAULTS)
@@ -503,6 +569,23 @@ def smooth_fit(**kwargs):
             raise NotImplementedError(f'smooth_fit: {key!r} is outside lssurf_amd (SURVEY.md §2)')
     if args.get('data_slope_sensors') is not None and len(args['data_slope_sensors']) > 0:
         raise NotImplementedError("smooth_fit: 'data_slope_sensors' is outside lssurf_amd")
+    bias_mode = args['lsq_bias']
+    if args['bias_params'] is not None:
+        if bias_mode is None:
+            raise NotImplementedError("smooth_fit: 'bias_params' needs the solver key lsq_bias ('eliminate', "
+                                      "'columns' or 'auto'); without it data biases are outside lssurf_amd")
+        if bias_mode not in ('eliminate', 'columns', 'auto'):
+            raise ValueError(f"smooth_fit: lsq_bias must be 'eliminate', 'columns' or 'auto', not {bias_mode!r}")
+        if args['compute_E']:
+            raise NotImplementedError("smooth_fit: compute_E with bias_params (sigma_bias) is outside lssurf_amd")
+        if int(args['n_gpus']) > 1 or (args['devices'] is not None and len(args['devices']) > 1):
+            raise NotImplementedError("smooth_fit: bias_params runs on one GPU")
+        if bias_mode == 'eliminate' and args['lsq_method'] == 'lsqr':
+            raise NotImplementedError("smooth_fit: lsq_bias='eliminate' runs CGNR; lsq_method='lsqr' needs "
+                                      "lsq_bias='columns'")
+        if bias_mode == 'eliminate' and args['lsq_precond'] not in ('auto', 1, 3, 4):
+            raise NotImplementedError("smooth_fit: lsq_bias='eliminate' runs CGNR with lsq_precond 'auto', 1, 3 or "
+                                      "4; the dense preconditioner needs lsq_bias='columns'")
 
     valid_data = np.isfinite(args['data'].z)
     if 'sensor' not in args['data'].fields:
@@ -537,8 +620,10 @@ def smooth_fit(**kwargs):
         return {'m': m, 'E': E, 'data': data, 'grids': grids, 'valid_data': valid_data, 'TOC': {}, 'R': {},
                 'RMS': {}, 'timing': timing, 'E_RMS': args['E_RMS']}
 
-    G_data = lin_op(grids['z0'], name='interp_z').interp_mtx(data.coords()[0:2])
-    G_data.add(lin_op(grids['dz'], name='interp_dz').interp_mtx(data.coords()))
+    def interp_ops():
+        G = lin_op(grids['z0'], name='interp_z').interp_mtx(data.coords()[0:2])
+        return G.add(lin_op(grids['dz'], name='interp_dz').interp_mtx(data.coords()))
+    G_data = interp_ops()
     constraint_op_list = []
     if args['VERBOSE']:
         print(f"smooth_fit: E_RMS={args['E_RMS']}")
@@ -548,6 +633,20 @@ def smooth_fit(**kwargs):
         if op.prior is None:
             op.prior = np.zeros(np.shape(op.expected))   # calloc: untouched pages (73 M rows at C4)
             zero_prior.add(op.name)
+    # data biases: one column per unique combination of the bias parameters behind the grids'
+    # columns, and their constraint rows last (smooth_fit.py:492-498).  G_grid / Gc_grid: the
+    # operators without them, which the device holds when it eliminates the biases itself
+    bias_model, G_grid, Gc_grid = {}, None, None
+    if args['bias_params'] is not None:
+        data, bias_model = assign_bias_ID(data, args['bias_params'], bias_filter=args['bias_filter'])
+        if bias_mode != 'columns':
+            G_grid = interp_ops()
+            Gc_grid = lin_op(None, name='constraints').vstack(list(constraint_op_list))
+        setup_bias_fit(data, bias_model, G_data, constraint_op_list, bias_param_name='bias_ID')
+        constraint_op_list[-1].prior = np.zeros(np.shape(constraint_op_list[-1].expected))
+        zero_prior.add(constraint_op_list[-1].name)
+        if args['bias_nsigma_edit']:
+            bias_model['bias_param_dict']['edited'] = np.zeros_like(bias_model['bias_param_dict']['ID'], dtype=bool)
     Gc = lin_op(None, name='constraints').vstack(constraint_op_list)
     N_eq = G_data.N_eq + Gc.N_eq
     Ed = data.sigma.ravel()
@@ -598,6 +697,9 @@ def smooth_fit(**kwargs):
                                   'path (one RCCL communicator per device) has been tested only as ranks '
                                   'sharing one device; see INTEGRATION.md §5', RuntimeWarning, stacklevel=2)
                 system = MultiDeviceFitSystem(G_data, Gc, keep_cols, Gc.col_N, devices)
+            elif bias_model:
+                system = _bias_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, bias_model, bias_mode, grids,
+                                          devices[0], args)
             else:
                 system = FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=devices[0], grids=grids)
             system.b_rows = b_rows
@@ -605,7 +707,8 @@ def smooth_fit(**kwargs):
             tic_iteration = time()
             m0, sigma_extra, in_TSE, rs_data = iterate_fit(data, system, rhs, TCinv_diag, G_data, Gc, in_TSE,
                                                            timing, args, grids,
-                                                           sigma_extra_masks=args['sigma_extra_masks'])
+                                                           sigma_extra_masks=args['sigma_extra_masks'],
+                                                           bias_model=bias_model)
             timing['iteration'] = time() - tic_iteration
             valid_data[valid_data] = in_TSE
             data.assign({'three_sigma_edit': in_TSE})
@@ -621,6 +724,8 @@ def smooth_fit(**kwargs):
             averaging_ops.update(setup_z0_avg(grids, grids['dz'].col_N, args))
             averaging_ops.update(setup_avg_mask_ops(grids['dz'], G_data.col_N, args['avg_masks'], args['dzdt_lags']))
             parse_model(m, m0, data, R, RMS, G_data, averaging_ops, Gc, Ec, grids, args, system=system)
+            if bias_model:   # the biases, in the order of the bias IDs (smooth_fit.py:309-310)
+                m['bias'], m['slope_bias'] = parse_biases(m0, bias_model, args['bias_params'], data=data)
             tse = data.three_sigma_edit == 1
             r_data = data.z_est[tse] - data.z[tse]
             R['data'] = np.sum((r_data / data.sigma[tse]) ** 2)
@@ -646,8 +751,11 @@ def smooth_fit(**kwargs):
     finally:
         if system is not None:
             system.close()
-    return {'m': m, 'E': E, 'data': data, 'grids': grids, 'valid_data': valid_data, 'TOC': Gc.TOC, 'R': R,
-            'RMS': RMS, 'timing': timing, 'E_RMS': args['E_RMS'], 'dzdt_lags': args['dzdt_lags']}
+    out = {'m': m, 'E': E, 'data': data, 'grids': grids, 'valid_data': valid_data, 'TOC': Gc.TOC, 'R': R,
+           'RMS': RMS, 'timing': timing, 'E_RMS': args['E_RMS'], 'dzdt_lags': args['dzdt_lags']}
+    if bias_model:   # beyond the reference's keys: the bias model, with the IDs edit_by_bias removed
+        out['bias_model'] = bias_model
+    return out
 
 
 # re-exported for callers that build Ip_c explicitly (smooth_fit.py:624)

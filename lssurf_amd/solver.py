@@ -27,6 +27,7 @@ class LSQSolver:
             raise NativeError(f'lsq_create({device}) failed: no gfx950 (MI355X) device visible')
         self.device = device
         self.m = self.n = self.n_full = None
+        self._n_bias = 0           # bias IDs set by set_data_bias
 
     # ---- lifetime --------------------------------------------------------------------------
     def close(self):
@@ -242,6 +243,26 @@ class LSQSolver:
         q = np.zeros(self.n_full)
         self._check(self._L.lsq_normal_apply(self._h, ptr(p), ptr(q)), 'lsq_normal_apply')
         return q
+
+    def set_data_bias(self, ids, c):
+        """One additive bias per ID on the data rows, eliminated inside CGNR (lsq_set_data_bias).
+
+        ids: the bias ID of every data row (caller's row order), in [0, len(c)); c: 1 / expected
+        bias size per ID, > 0.  ids = None (or an empty c) clears the biases."""
+        if ids is None or c is None or np.size(c) == 0:
+            self._check(self._L.lsq_set_data_bias(self._h, 0, None, 0, None), 'lsq_set_data_bias')
+            self._n_bias = 0
+            return
+        ids = as_c(ids, np.int32)
+        c = as_c(c, np.float64)
+        self._check(self._L.lsq_set_data_bias(self._h, ids.size, ptr(ids), c.size, ptr(c)), 'lsq_set_data_bias')
+        self._n_bias = int(c.size)
+
+    def data_bias(self):
+        """The biases that belong to the last solve's x (one per ID)."""
+        b = np.zeros(max(self._n_bias, 1))
+        self._check(self._L.lsq_get_data_bias(self._h, ptr(b)), 'lsq_get_data_bias')
+        return b[:self._n_bias]
 
     def info(self):
         o = np.zeros(8, np.int64)
