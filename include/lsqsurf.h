@@ -155,6 +155,35 @@ int lsq_set_matrix_stencil(lsq_handle* h, int64_t m, int64_t n_full,
 int lsq_set_stencil_fields(lsq_handle* h, int32_t stencil, int32_t ntpl, const int32_t* off, const double* val,
                            int32_t nfield, const int32_t* fsel, int64_t n_eq, const double* F);
 
+/* Extra sparse rows behind the stencil rows, staged before lsq_set_matrix_stencil (and after
+ * lsq_set_col_map): the m_x rows of the CSR (indptr, cols_full, vals), columns = full-space ids,
+ * become the LAST rows of the system, so m of lsq_set_matrix_stencil is data rows + stencil rows +
+ * m_x.  These are rows that are neither interpolation rows nor stencil rows, e.g. smooth_fit's dz
+ * priors (interp_dz(y, x, t) − interp_dz(y, x, t_ref) with their own σ and a non-zero b).
+ * Formation follows lsq_set_matrix_coo: duplicates within a row are summed in input order, zeros and
+ * zero sums are dropped, entries in columns the col map removes are dropped; a row may end up empty.
+ * A row that keeps more than 32 entries returns −2 and the staging stays as it was.  m_x = 0 or a
+ * null indptr clears the staging.  Row weights, the row mask and b address these rows at their
+ * positions; lsq_shape counts them; lsq_get_csr / lsq_spmv / lsq_spmv_rows, the dense (2) and band
+ * (5) factors and LSQR on the assembled operator (op = 1) cover them through the full CSR.
+ * Matrix-free CGNR (method 1) carries them with precond 1 or 3: the normal operator gains
+ * XᵀW_x²X (two small kernels per step, bitwise reproducible), the Jacobi norms and the node-block
+ * factors gain the same sums, and lsq_normal_apply includes the term.  With lsq_opts.b_rows the
+ * library also uploads b[m − m_x, m).  Refused with −2 and the reason: precond 4 (the multigrid's
+ * coarse levels would miss the term; lsq_cg_available(h, 4) reports 0), LSQR on the structured
+ * stencil operator (op = 0 on a lazily formed system), tile-mode CGNR, and every distributed,
+ * virtual or device-group rank (the formation itself is refused there).  May be combined with
+ * lsq_set_data_bias: the two terms are independent.
+ * lsq_extra_rows_info: out4 = {m_x, touched columns, algorithmic bytes of one CG step's two
+ * kernels, device bytes of the rows and their transpose}.
+ * lsq_profile_extra_rows: after lsq_iterate with the same precond (its live state), runs reps more
+ * iterations with device events between the launches: out4 = {ms k_xr_fwd, ms k_xr_atq (with its
+ * long-column kernel), ms of the data rows' Ad·p before them, ms of the node gather behind them}. */
+int lsq_set_extra_rows(lsq_handle* h, int64_t m_x, const int64_t* indptr, const int64_t* cols_full,
+                       const double* vals);
+int lsq_extra_rows_info(lsq_handle* h, double* out4);
+int lsq_profile_extra_rows(lsq_handle* h, int32_t reps, int32_t precond, double* out4);
+
 /* Replace the row weights (TCinv of iterate_fit, smooth_fit.py:123-129) without re-forming. */
 int lsq_set_row_weight(lsq_handle* h, const double* row_weight);
 /* Row selection Ip_r (smooth_fit.py:132-135): rows with keep[i] == 0 are excluded from the

@@ -50,7 +50,8 @@ class LsqStats(ctypes.Structure):
 
 # every symbol declared in include/lsqsurf.h
 EXPORTS = ['lsq_default_opts', 'lsq_create', 'lsq_destroy', 'lsq_last_error', 'lsq_set_col_map',
-           'lsq_set_matrix_coo', 'lsq_set_matrix_stencil', 'lsq_set_stencil_fields', 'lsq_set_row_weight',
+           'lsq_set_matrix_coo', 'lsq_set_matrix_stencil', 'lsq_set_stencil_fields', 'lsq_set_extra_rows', 'lsq_extra_rows_info',
+           'lsq_profile_extra_rows', 'lsq_set_row_weight',
            'lsq_set_row_mask',
            'lsq_set_column_blocks', 'lsq_set_column_blocks_affine', 'lsq_shape', 'lsq_get_csr', 'lsq_release_full_csr',
            'lsq_solve', 'lsq_spmv', 'lsq_spmv_rows', 'lsq_rows_sumsq', 'lsq_data_colsum', 'lsq_iterate', 'lsq_profile_kernels', 'lsq_cg_available', 'lsq_profile_cg', 'lsq_mg_info', 'lsq_mg_apply', 'lsq_normal_apply', 'lsq_set_data_bias', 'lsq_get_data_bias', 'lsq_sell_info', 'lsq_sigma_x', 'lsq_cov_band', 'lsq_cov_band_window', 'lsq_cov_band_windows', 'lsq_cov_band_windows_schur', 'lsq_set_band_order', 'lsq_band_factor',
@@ -104,6 +105,9 @@ def load():
         'lsq_mg_apply': ([P, i32, i32, P, P], ctypes.c_int),
         'lsq_normal_apply': ([P, P, P], ctypes.c_int),
         'lsq_set_data_bias': ([P, i64, P, i64, P], ctypes.c_int),
+        'lsq_set_extra_rows': ([P, i64, P, P, P], ctypes.c_int),
+        'lsq_extra_rows_info': ([P, P], ctypes.c_int),
+        'lsq_profile_extra_rows': ([P, i32, i32, P], ctypes.c_int),
         'lsq_get_data_bias': ([P, P], ctypes.c_int),
         'lsq_sell_info': ([P, P], ctypes.c_int),
         'lsq_sigma_x': ([P, P], ctypes.c_int),

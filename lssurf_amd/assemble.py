@@ -77,10 +77,25 @@ def _merge_group(group, n_eq):
             np.ascontiguousarray(np.stack(fields)))
 
 
-def describe(G_data, Gc, with_fields=False):
+def extra_rows_of(Gc):
+    """Rows of Gc held by its trailing parts of kind 'extra' (match_priors.make_prior_op): they
+    must be the last rows, in one run; 0 when there are none or the parts are unknown."""
+    if not Gc.parts:
+        return 0
+    n = 0
+    for p in reversed(Gc.parts):
+        if p['kind'] != 'extra' or p['row0'] + p['n_eq'] != Gc.N_eq - n:
+            break
+        n += int(p['n_eq'])
+    return n
+
+
+def describe(G_data, Gc, with_fields=False, extra_rows=False):
     """(grids, interp_grid_ids, (py, px, pt), stencils, npts) or None if not structured;
     with_fields: a sixth element, the field-valued parts [(stencil index, off, val, fsel, F)]
-    (None is returned for such operators when with_fields is False)."""
+    (None is returned for such operators when with_fields is False).
+    extra_rows: trailing parts of kind 'extra' (prior rows) are left out of the description, which
+    then covers the other rows; the caller stages them with LSQSolver.set_extra_rows."""
     if G_data.parts is None or Gc.parts is None or not G_data.parts:
         return None
     grids, index = [], {}
@@ -105,7 +120,10 @@ def describe(G_data, Gc, with_fields=False):
             coords = pts
     # stencil parts, grouped by row set (parts added onto the same rows are consecutive)
     groups = []
+    n_extra = extra_rows_of(Gc) if extra_rows else 0
     for p in Gc.parts:
+        if p['kind'] == 'extra' and p['row0'] >= Gc.N_eq - n_extra:
+            continue
         if p['kind'] != 'stencil' or p.get('row_base', 0) != 0:
             return None
         key = (id(p['grid']), int(p['row0']), int(p['n_eq']), tuple(p['lo']), tuple(p['hi']))

@@ -14,12 +14,15 @@ bool cg_available(System& S, int precond);
 int cg_solve(System& S, const double* h_b, double* h_x, const lsq_opts& o, lsq_stats* stats);
 int cg_iterate(System& S, const double* h_b, int64_t iters, const lsq_opts& o, lsq_stats* stats);
 void cg_profile(System& S, int reps, int precond, double* out);
+void cg_profile_xr(System& S, int reps, int precond, double* out);
 void cg_apply_normal(System& S, const double* h_p, double* h_q);
 void cg_data_colsum(System& S, const double* h_f, double* h_out);
 void bias_set(System& S, int64_t npts, const int32_t* h_id, int64_t nb, const double* h_c);
 void bias_clear(System& S);
 void bias_get(System& S, double* h_b);
 std::string bias_refusal(System& S, int method, int precond);
+std::string xr_refusal(System& S, int method, int precond, int op);
+void xr_info(System& S, double* out4);
 int lsqr_iterate(System& S, const double* h_b, int64_t iters, const lsq_opts& o, lsq_stats* stats);
 void lsqr_profile(System& S, int reps, int op, double* out);
 void lsqr_sigma_x(System& S, double* h_E);
@@ -135,6 +138,9 @@ int lsq_set_matrix_coo(lsq_handle* h, int64_t m, int64_t n_full, int64_t nnz, co
         if (m >= (int64_t)INT32_MAX || n_full >= (int64_t)INT32_MAX)
             return fail(S, "lsq_set_matrix_coo: dimensions must fit int32 column indices");
         if (S.G.rp.p) return fail(S, "lsq_set_matrix_coo: matrix already set (create a new handle)");
+        if (S.xr.st_m > 0)   // only the structured formation takes them: never drop staged rows silently
+            return fail(S, "lsq_set_matrix_coo: extra rows are staged (lsq_set_extra_rows); they go with "
+                           "lsq_set_matrix_stencil - clear them (m_x = 0) or put the rows in the triplets");
         lsq::graph_cache_drop(&S);
         lsq::form_from_coo(S, m, n_full, nnz, r, c, v);
         if (row_weight) {
@@ -192,6 +198,73 @@ int lsq_set_stencil_fields(lsq_handle* h, int32_t stencil, int32_t ntpl, const i
         f.F.upload(F, (int64_t)nfield * n_eq, S.stream);
         HIP_CHECK(hipStreamSynchronize(S.stream));
         S.sfields.push_back(std::move(f));
+        return 0;
+    });
+}
+
+int lsq_set_extra_rows(lsq_handle* h, int64_t m_x, const int64_t* indptr, const int64_t* cols_full,
+                       const double* vals) {
+    return guarded(h, [&](lsq::System& S) {
+        if (S.G.rp.p) return fail(S, "lsq_set_extra_rows must precede lsq_set_matrix_stencil");
+        lsq::XrData& X = S.xr;
+        if (m_x <= 0 || !indptr) {   // clears the staging
+            X.st_m = 0;
+            X.st_rp.clear();
+            X.st_ci.clear();
+            X.st_val.clear();
+            return 0;
+        }
+        if (indptr[0] != 0 || (indptr[m_x] && (!cols_full || !vals)))
+            return fail(S, "lsq_set_extra_rows: bad arguments");
+        std::vector<int32_t> cmap;
+        if (S.have_colmap) {
+            cmap.resize(S.n_full);
+            S.colmap.download(cmap.data(), S.n_full, S.stream);
+            HIP_CHECK(hipStreamSynchronize(S.stream));
+        }
+        // the rules of lsq_set_matrix_coo per row: duplicates summed in input order, zeros and zero
+        // sums dropped, entries in columns the col map removes dropped; columns ascending
+        std::vector<int64_t> rp(m_x + 1, 0), ci;
+        std::vector<double> val;
+        std::vector<std::pair<int64_t, double>> row;
+        for (int64_t r = 0; r < m_x; ++r) {
+            if (indptr[r + 1] < indptr[r]) return fail(S, "lsq_set_extra_rows: indptr must not decrease");
+            row.clear();
+            for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
+                const int64_t c = cols_full[e];
+                if (c < 0 || c >= (int64_t)INT32_MAX || (S.have_colmap && c >= S.n_full))
+                    return fail(S, "lsq_set_extra_rows: column out of range");
+                size_t k = 0;
+                while (k < row.size() && row[k].first != c) ++k;
+                if (k == row.size())
+                    row.emplace_back(c, vals[e]);
+                else
+                    row[k].second += vals[e];
+            }
+            std::sort(row.begin(), row.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+            for (const auto& cv : row) {
+                if (cv.second == 0.0 || (S.have_colmap && cmap[cv.first] < 0)) continue;
+                ci.push_back(cv.first);
+                val.push_back(cv.second);
+            }
+            rp[r + 1] = (int64_t)ci.size();
+            if (rp[r + 1] - rp[r] > lsq::XR_MAXW)
+                return fail(S, "lsq_set_extra_rows: row " + std::to_string(r) + " keeps more than " +
+                                   std::to_string(lsq::XR_MAXW) + " entries");
+        }
+        X.st_m = m_x;
+        X.st_rp = std::move(rp);
+        X.st_ci = std::move(ci);
+        X.st_val = std::move(val);
+        return 0;
+    });
+}
+
+int lsq_extra_rows_info(lsq_handle* h, double* out4) {
+    return guarded(h, [&](lsq::System& S) {
+        if (!S.G.rp.p) return fail(S, "lsq_extra_rows_info: no matrix");
+        if (!out4) return fail(S, "lsq_extra_rows_info: null output");
+        lsq::xr_info(S, out4);
         return 0;
     });
 }
@@ -306,6 +379,10 @@ int lsq_solve(lsq_handle* h, const double* b, double* x_inout, const lsq_opts* o
             const std::string why = lsq::bias_refusal(S, o->method, o->precond);
             if (!why.empty()) return fail(S, "lsq_solve: " + why);
         }
+        if (S.xr.m_x) {
+            const std::string why = lsq::xr_refusal(S, o->method, o->precond, o->op);
+            if (!why.empty()) return fail(S, "lsq_solve: " + why);
+        }
         if (o->precond == 4 && (o->method != 1 || (!S.dist && !lsq::cg_available(S, 4))))
             return fail(S, "lsq_solve: precond 4 (multigrid) runs CGNR (method 1) on structured systems: " +
                                (o->method != 1 ? std::string("method is not 1") : S.cg_ok ? S.mg_why : S.cg_why));
@@ -343,6 +420,10 @@ int lsq_iterate(lsq_handle* h, const double* b, int64_t iters, const lsq_opts* o
             const std::string why = lsq::bias_refusal(S, o->method, o->precond);
             if (!why.empty()) return fail(S, "lsq_iterate: " + why);
         }
+        if (S.xr.m_x) {
+            const std::string why = lsq::xr_refusal(S, o->method, o->precond, o->op);
+            if (!why.empty()) return fail(S, "lsq_iterate: " + why);
+        }
         if (o->precond == 4 && (o->method != 1 || (!S.dist && !lsq::cg_available(S, 4))))
             return fail(S, "lsq_iterate: precond 4 (multigrid) runs CGNR (method 1) on structured systems: " +
                                (o->method != 1 ? std::string("method is not 1") : S.cg_ok ? S.mg_why : S.cg_why));
@@ -372,7 +453,20 @@ int lsq_cg_available(lsq_handle* h, int32_t precond) {
                 return 0;
             }
         }
-        if (lsq::cg_available(S, precond)) return 1;
+        if (S.xr.m_x && precond == 4) {   // the coarse levels would not carry the extra rows' term
+            S.err = lsq::xr_refusal(S, 1, 4, 0);
+            return 0;
+        }
+        if (lsq::cg_available(S, precond)) {
+            if (S.xr.m_x) {
+                const std::string why = lsq::xr_refusal(S, 1, precond, 0);
+                if (!why.empty()) {
+                    S.err = why;
+                    return 0;
+                }
+            }
+            return 1;
+        }
         S.err = !S.cg_ok ? (S.cg_why.empty() ? "not a structured single-GPU system" : S.cg_why) : S.mg_why;
         return 0;
     });
@@ -385,6 +479,16 @@ int lsq_profile_cg(lsq_handle* h, int32_t reps, int32_t precond, double* out8) {
         if (!lsq::cg_available(S, precond)) return fail(S, "lsq_profile_cg: CGNR not available: " + S.cg_why);
         lsq::graph_cache_drop(&S);
         lsq::cg_profile(S, reps > 0 ? reps : 10, precond, out8);
+        return 0;
+    });
+}
+
+int lsq_profile_extra_rows(lsq_handle* h, int32_t reps, int32_t precond, double* out4) {
+    return guarded(h, [&](lsq::System& S) {
+        if (!S.G.rp.p) return fail(S, "lsq_profile_extra_rows: no matrix");
+        if (!out4) return fail(S, "lsq_profile_extra_rows: null output");
+        lsq::graph_cache_drop(&S);
+        lsq::cg_profile_xr(S, reps > 0 ? reps : 10, precond, out4);
         return 0;
     });
 }
@@ -411,6 +515,10 @@ int lsq_normal_apply(lsq_handle* h, const double* p, double* q) {
         if (!S.G.rp.p) return fail(S, "lsq_normal_apply: no matrix");
         if (!p || !q) return fail(S, "lsq_normal_apply: null vector");
         if (!lsq::cg_available(S, 1)) return fail(S, "lsq_normal_apply: no normal-stencil operator: " + S.cg_why);
+        if (S.xr.m_x) {
+            const std::string why = lsq::xr_refusal(S, 1, 1, 0);
+            if (!why.empty()) return fail(S, "lsq_normal_apply: " + why);
+        }
         lsq::cg_apply_normal(S, p, q);
         return 0;
     });

@@ -366,6 +366,35 @@ void describe_global(System& S, int64_t n_full, int32_t n_grids, const lsq_grid_
 
 namespace {
 
+// The formed extra rows (lsq_set_extra_rows; XrData::h_*) appended behind the generated rows of a
+// fully formed G: the system's last rows
+void append_extra_rows(System& S, int64_t m_gen) {
+    const XrData& X = S.xr;
+    hipStream_t strm = S.stream;
+    Csr& G = S.G;
+    const int64_t z0 = G.nnz, zx = X.nnz;
+    std::vector<int64_t> tail(X.m_x);
+    for (int64_t r = 0; r < X.m_x; ++r) tail[r] = z0 + X.h_rp[r + 1];
+    DBuf<int64_t> rp(m_gen + X.m_x + 1);
+    DBuf<int32_t> ci(std::max<int64_t>(z0 + zx, 1));
+    DBuf<double> val(std::max<int64_t>(z0 + zx, 1));
+    HIP_CHECK(hipMemcpyAsync(rp.p, G.rp.p, sizeof(int64_t) * (m_gen + 1), hipMemcpyDeviceToDevice, strm));
+    HIP_CHECK(hipMemcpyAsync(rp.p + m_gen + 1, tail.data(), sizeof(int64_t) * X.m_x, hipMemcpyHostToDevice, strm));
+    if (z0) {
+        HIP_CHECK(hipMemcpyAsync(ci.p, G.ci.p, sizeof(int32_t) * z0, hipMemcpyDeviceToDevice, strm));
+        HIP_CHECK(hipMemcpyAsync(val.p, G.val.p, sizeof(double) * z0, hipMemcpyDeviceToDevice, strm));
+    }
+    if (zx) {
+        HIP_CHECK(hipMemcpyAsync(ci.p + z0, X.h_ci.data(), sizeof(int32_t) * zx, hipMemcpyHostToDevice, strm));
+        HIP_CHECK(hipMemcpyAsync(val.p + z0, X.h_val.data(), sizeof(double) * zx, hipMemcpyHostToDevice, strm));
+    }
+    HIP_CHECK(hipStreamSynchronize(strm));   // tail is a local
+    G.rp = std::move(rp);
+    G.ci = std::move(ci);
+    G.val = std::move(val);
+    G.nnz = z0 + zx;
+}
+
 // G's row pointers for all m rows (count pass: validates every row and gives the formed nnz), then
 // the entries of the first `rows` rows (fill pass).  S.G.m = m either way; rows < m keeps npts + 1
 // row pointers (the lazy structured formation: rows = the data rows).
@@ -383,9 +412,9 @@ void gen_rows_csr(System& S, const double* dy, const double* dx, const double* d
     hipLaunchKernelGGL(k_gen_rows, dim3(grid_for(m)), dim3(BLOCK), 0, strm, 0, dctx.p, dy, dx, dt, cmap, rp.p, nullptr,
                        nullptr, nullptr, err.p, m);
     KERNEL_CHECK();
-    S.nnz_full = exclusive_scan_i64(rp.p, m + 1, strm);
+    S.nnz_full = exclusive_scan_i64(rp.p, m + 1, strm) + S.xr.nnz;
     Csr& G = S.G;
-    G.m = m;
+    G.m = m + S.xr.m_x;   // the extra rows (lsq_set_extra_rows) follow the generated ones
     G.n = S.have_colmap ? S.n_keep : h.n_full;
     if (rows < m) {
         G.rp.alloc(rows + 1);
@@ -394,7 +423,7 @@ void gen_rows_csr(System& S, const double* dy, const double* dx, const double* d
         HIP_CHECK(hipStreamSynchronize(strm));   // rp is released below
     } else {
         G.rp = std::move(rp);
-        G.nnz = S.nnz_full;
+        G.nnz = S.nnz_full - S.xr.nnz;
     }
     G.ci.alloc(std::max<int64_t>(G.nnz, 1));
     G.val.alloc(std::max<int64_t>(G.nnz, 1));
@@ -407,6 +436,7 @@ void gen_rows_csr(System& S, const double* dy, const double* dx, const double* d
     HIP_CHECK(hipStreamSynchronize(strm));
     if (herr) throw std::invalid_argument("lsq_set_matrix_stencil: " + std::to_string(herr) +
                                           " nonzero entries fall outside [0, n_full)");
+    if (rows == m && S.xr.m_x) append_extra_rows(S, m);
 }
 
 }  // namespace
@@ -417,6 +447,10 @@ void form_from_stencils(System& S, int64_t m, int64_t n_full, int32_t n_grids, c
     if (n_grids < 1 || n_grids > MAX_GRIDS || n_interp < 0 || n_interp > MAX_INTERP || n_stencil < 0 ||
         n_stencil > MAX_STENCIL)
         throw std::invalid_argument("lsq_set_matrix_stencil: too many grids / parts");
+    // extra rows staged by lsq_set_extra_rows are the last rows: the generator sees the rest
+    const int64_t m_x = S.xr.st_m;
+    if (m_x > m - npts) throw std::invalid_argument("lsq_set_matrix_stencil: m is smaller than the data and extra rows");
+    m -= m_x;
     GenCtx h{};
     h.n_grids = n_grids;
     h.n_interp = n_interp;
@@ -481,7 +515,9 @@ void form_from_stencils(System& S, int64_t m, int64_t n_full, int32_t n_grids, c
         if (ext != st[s].n_eq) throw std::invalid_argument("stencil n_eq does not match its centre box");
         expect += st[s].n_eq;
     }
-    if (expect != m) throw std::invalid_argument("rows of the parts do not add up to m");
+    if (expect != m)
+        throw std::invalid_argument(m_x ? "rows of the parts and the extra rows do not add up to m"
+                                        : "rows of the parts do not add up to m");
     if (npts > 0 && (!py || !px || (need_t && !pt))) throw std::invalid_argument("missing point coordinates");
 
     hipStream_t strm = S.stream;
@@ -492,6 +528,12 @@ void form_from_stencils(System& S, int64_t m, int64_t n_full, int32_t n_grids, c
                                     "(single GPU, parts inside their grids, |offsets| <= 3)");
     // structured single-GPU systems store only the data rows (System::g_full; LSQ_FULL_CSR=1 forms
     // everything up front, for A/B)
+    if (m_x && !S.mf)
+        throw std::invalid_argument("lsq_set_matrix_stencil: extra rows need the structured single-GPU operator");
+    S.xr.m_x = 0;
+    S.xr.nnz = 0;
+    S.xr.on = false;
+    if (m_x) xr_form(S, m);
     static const bool full_env = getenv("LSQ_FULL_CSR") && getenv("LSQ_FULL_CSR")[0] == '1';
     const bool lazy = S.mf && !full_env;
     DBuf<double> dy(std::max<int64_t>(npts, 1)), dx(std::max<int64_t>(npts, 1)), dt;
@@ -521,7 +563,7 @@ void form_from_stencils(System& S, int64_t m, int64_t n_full, int32_t n_grids, c
 void ensure_full_csr(System& S) {
     if (S.g_full) return;
     graph_cache_drop(&S);   // G is reallocated (a captured batch may hold the data-row CSR's pointers)
-    gen_rows_csr(S, S.gen_py.p, S.gen_px.p, S.gen_pt.n ? S.gen_pt.p : nullptr, S.G.m);
+    gen_rows_csr(S, S.gen_py.p, S.gen_px.p, S.gen_pt.n ? S.gen_pt.p : nullptr, S.G.m - S.xr.m_x);
     S.g_full = true;
     // the generation context stays (24 B per data row) so release_full_csr can drop G / GT again
     full_transpose(S);
@@ -549,8 +591,8 @@ int64_t stored_rows(const System& S) { return S.g_full ? S.G.m : S.mfh.npts; }
 // against the row mask (shape() used to form and keep the full G / GT).
 void shape_counts(System& S, int64_t* mk, int64_t* zk) {
     hipStream_t strm = S.stream;
-    const int64_t m = S.G.m;
     if (S.g_full) {
+        const int64_t m = S.G.m;
         std::vector<int64_t> rp(m + 1);
         std::vector<uint8_t> keep(m);
         S.G.rp.download(rp.data(), m + 1, strm);
@@ -564,6 +606,7 @@ void shape_counts(System& S, int64_t* mk, int64_t* zk) {
         return;
     }
     const GenCtx& h = *reinterpret_cast<const GenCtx*>(S.gen_ctx.data());
+    const int64_t m_x = S.xr.m_x, m = S.G.m - m_x;   // generated rows; the extra rows are counted below
     DBuf<GenCtx> dctx(1);
     HIP_CHECK(hipMemcpyAsync(dctx.p, &h, sizeof(GenCtx), hipMemcpyHostToDevice, strm));
     DBuf<unsigned long long> err(1), ks(2);
@@ -576,9 +619,16 @@ void shape_counts(System& S, int64_t* mk, int64_t* zk) {
     KERNEL_CHECK();
     unsigned long long v[2] = {0, 0};
     ks.download(v, 2, strm);
+    std::vector<uint8_t> xkeep(m_x);
+    if (m_x) HIP_CHECK(hipMemcpyAsync(xkeep.data(), S.rowkeep.p + m, m_x, hipMemcpyDeviceToHost, strm));
     HIP_CHECK(hipStreamSynchronize(strm));
     *mk = (int64_t)v[0];
     *zk = (int64_t)v[1];
+    for (int64_t r = 0; r < m_x; ++r)
+        if (xkeep[r]) {
+            ++*mk;
+            *zk += S.xr.h_rp[r + 1] - S.xr.h_rp[r];
+        }
 }
 
 // z0 (gz) on a 2× refinement of the dz (g3) lattice: the points sorted by dz cell with their dz

@@ -399,6 +399,53 @@ __global__ __launch_bounds__(BLOCK) void k_block_rinv32(int64_t nb, int npk, int
     }
 }
 
+// Extra rows (lsq_set_extra_rows) of a lazily formed system: their part of (AᵀA)_bb.
+// k_xr_blk_mark: tblk[j] = the block that holds touched column tc[j] (−1: none), one thread per block
+// column, a binary search in the ascending touched list.
+__device__ __forceinline__ int64_t xr_find(const int32_t* __restrict__ tc, int64_t ntc, int32_t f) {
+    int64_t lo = 0, hi = ntc;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (tc[mid] < f) lo = mid + 1; else hi = mid;
+    }
+    return lo < ntc && tc[lo] == f ? lo : -1;
+}
+__global__ __launch_bounds__(BLOCK) void k_xr_blk_mark(int64_t nb, const int64_t* __restrict__ ptr,
+                                                       const int32_t* __restrict__ full, int64_t ntc,
+                                                       const int32_t* __restrict__ tc, int32_t* __restrict__ tblk) {
+    for (int64_t b = (int64_t)blockIdx.x * BLOCK + threadIdx.x; b < nb; b += (int64_t)gridDim.x * BLOCK)
+        for (int64_t e = ptr[b]; e < ptr[b + 1]; ++e) {
+            const int64_t j = xr_find(tc, ntc, full[e]);
+            if (j >= 0) tblk[j] = (int32_t)b;
+        }
+}
+// k_xr_blk_add: one thread per (touched column j, position jj of its block): with i the position of
+// tc[j] in the block, the pair (i, jj), i ≤ jj, both touched, gains the col_dot merge over the
+// transpose.  Each packed entry belongs to one thread: no atomics, a fixed order.
+__global__ __launch_bounds__(BLOCK) void k_xr_blk_add(int64_t ntc, int kmax, const int64_t* __restrict__ ptr,
+                                                      const int32_t* __restrict__ full,
+                                                      const int32_t* __restrict__ tc, const int32_t* __restrict__ tblk,
+                                                      const int64_t* __restrict__ cp, const int32_t* __restrict__ cr,
+                                                      const double* __restrict__ cv, const double* __restrict__ rs,
+                                                      double* __restrict__ N) {
+    const int npk = kmax * (kmax + 1) / 2;
+    for (int64_t q = (int64_t)blockIdx.x * BLOCK + threadIdx.x; q < ntc * kmax; q += (int64_t)gridDim.x * BLOCK) {
+        const int64_t j = q / kmax;
+        const int jj = (int)(q - j * kmax);
+        const int32_t b = tblk[j];
+        if (b < 0) continue;
+        const int64_t b0 = ptr[b];
+        const int k = (int)(ptr[b + 1] - b0);
+        if (jj >= k) continue;
+        int i = 0;
+        while (i < k && full[b0 + i] != tc[j]) ++i;
+        if (i > jj) continue;
+        const int64_t j2 = i == jj ? j : xr_find(tc, ntc, full[b0 + jj]);
+        if (j2 < 0) continue;
+        N[(int64_t)b * npk + pk(i, jj)] += col_dot(cp, cr, cv, rs, (int32_t)j, (int32_t)j2);
+    }
+}
+
 __global__ __launch_bounds__(BLOCK) void k_full_ids(int64_t n, const int32_t* __restrict__ cols,
                                                     const int32_t* __restrict__ keep, int32_t* __restrict__ out) {
     for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK)
@@ -594,6 +641,18 @@ void block_normal(System& S) {
         hipLaunchKernelGGL(k_block_normal, dim3(grid_for(S.nblk * npk)), dim3(BLOCK), 0, S.stream, S.nblk, S.blk_kmax,
                            S.blk_ptr.p, S.blk_cols.p, S.GT.rp.p, S.GT.ci.p, S.GT.val.p, S.rs.p, S.blk_Ri.p);
     KERNEL_CHECK();
+    // a lazily formed system's extra rows (lsq_set_extra_rows) are in neither GdT nor the parts; the
+    // full GT above holds them
+    if (!S.g_full && S.xr.on) {
+        const XrData& X = S.xr;
+        HIP_CHECK(hipMemsetAsync(X.tblk.p, 0xff, X.tblk.bytes(), S.stream));
+        hipLaunchKernelGGL(k_xr_blk_mark, dim3(grid_for(S.nblk)), dim3(BLOCK), 0, S.stream, S.nblk, S.blk_ptr.p,
+                           S.blk_full.p, X.ntc, X.tc.p, X.tblk.p);
+        hipLaunchKernelGGL(k_xr_blk_add, dim3(grid_for(X.ntc * S.blk_kmax)), dim3(BLOCK), 0, S.stream, X.ntc, S.blk_kmax,
+                           S.blk_ptr.p, S.blk_full.p, X.tc.p, X.tblk.p, X.cp.p, X.cr.p, X.cv.p, S.rs.p + X.row0,
+                           S.blk_Ri.p);
+        KERNEL_CHECK();
+    }
 }
 
 // blk_Ri: (AᵀA)_bb -> R_b⁻¹ in place

@@ -880,6 +880,8 @@ void csr_spmv_rows(System& S, int64_t first, int64_t count, const double* dx, do
 void csr_rows_sumsq(System& S, const double* dx, int64_t first, int64_t count, double* h_w, double* h_u) {
     const int nb = grid_for(std::max<int64_t>(count, 1));
     DBuf<double> pw(nb), pu(nb);
+    // a range that reaches the extra rows (no part descriptor generates them): from the full CSR
+    if (S.xr.m_x && !S.g_full && first + count > S.G.m - S.xr.m_x) ensure_full_csr(S);
     const int64_t ns = stored_rows(S);
     if (first + count <= ns) {
         hipLaunchKernelGGL(k_rows_sumsq, dim3(nb), dim3(BLOCK), 0, S.stream, first, count, S.G.rp.p, S.G.ci.p, S.G.val.p,

@@ -28,6 +28,7 @@ namespace {
 
 constexpr int NPART = 2048;   // partial-sum slots per reduction (fixed grid => deterministic)
 constexpr int BIAS_NPART = 64;   // further slots behind them: the data-bias elimination's partials (bias.inc)
+constexpr int XR_NPART = 512;    // and behind those: the extra rows' partials (xrows.inc)
 
 // ---- SELL-64 row kernel body: one lane = one row, 4 entries in flight per step -------------
 __device__ __forceinline__ double sell_row_dot(const int32_t* __restrict__ ci, const double* __restrict__ val,
@@ -443,6 +444,13 @@ void ensure_workspace(System& S) {
         S.part_b.alloc(NPART + BIAS_NPART);
         S.st.alloc(1);
     }
+    // extra rows set (xrows.inc): room for their partials behind the others; without them every
+    // buffer keeps the size it always had
+    if (S.xr.on && S.part_u.n < NPART + BIAS_NPART + XR_NPART) {
+        graph_cache_drop(&S);
+        S.part_u.alloc(NPART + BIAS_NPART + XR_NPART);
+        S.part_b.alloc(NPART + BIAS_NPART + XR_NPART);
+    }
 }
 
 // launch one LSQR iteration; parity p: ṽ read from vb[p], written to vb[1-p]
@@ -534,7 +542,12 @@ const double* upload_rhs(System& S, const double* h_b, const lsq_opts& o, hipStr
     const int64_t m = S.G.m, nb = o.b_rows > 0 && o.b_rows < m ? o.b_rows : m;
     if (S.rhs.n < std::max<int64_t>(m, 1)) S.rhs.alloc(std::max<int64_t>(m, 1));
     S.rhs.upload(h_b, nb, st);
-    if (nb < m) HIP_CHECK(hipMemsetAsync(S.rhs.p + nb, 0, (size_t)(m - nb) * sizeof(double), st));
+    // extra rows (lsq_set_extra_rows) carry their own b: b_rows counts the leading rows only, and the
+    // zeros between them and the extra rows still stay on the host
+    const int64_t tail = nb < m ? std::max(nb, m - S.xr.m_x) : m;
+    if (nb < tail) HIP_CHECK(hipMemsetAsync(S.rhs.p + nb, 0, (size_t)(tail - nb) * sizeof(double), st));
+    if (tail < m) HIP_CHECK(hipMemcpyAsync(S.rhs.p + tail, h_b + tail, (size_t)(m - tail) * sizeof(double),
+                                           hipMemcpyHostToDevice, st));
     return S.rhs.p;
 }
 
@@ -761,6 +774,7 @@ void mf_column_scale(System& S, bool raw) {
     hipLaunchKernelGGL(k_mf_colnorm, dim3(grid_for(S.mfh.nodes)), dim3(BLOCK), 0, S.stream, S.mfd.p, S.ATd.perm.p,
                        S.GdT.rp.p, S.GdT.ci.p, S.GdT.val.p, S.rs.p, S.csf.p);
     KERNEL_CHECK();
+    if (S.xr.on) xr_add_colnorm(S, S.csf.p);   // the extra rows' share (xrows.inc)
     hipLaunchKernelGGL(k_norm_gather, dim3(grid_for(S.G.n)), dim3(BLOCK), 0, S.stream, S.G.n, S.keep.p, S.csf.p,
                        raw ? 1 : 0, S.cs.p);
     KERNEL_CHECK();

@@ -2000,7 +2000,12 @@ void cg_workspace(System& S) {
     const int npg = cg_grid_normal(S) + (S.cgh.colmode ? S.cgh.nedge : 0) + S.cg_nvb;
     if (S.cg_part_g.n != npg) S.cg_part_g.alloc(npg);
     if (!S.cg_part_r.p) S.cg_part_r.alloc(NPART);
-    if (!S.cg_part_t.p) S.cg_part_t.alloc(NPART + BIAS_NPART);   // the data rows' partials, then the biases'
+    // the data rows' partials, then the biases'; then (set: more room) the extra rows'
+    if (!S.cg_part_t.p) S.cg_part_t.alloc(NPART + BIAS_NPART);
+    if (S.xr.on && S.cg_part_t.n < NPART + BIAS_NPART + XR_NPART) {
+        graph_cache_drop(&S);
+        S.cg_part_t.alloc(NPART + BIAS_NPART + XR_NPART);
+    }
     if (!S.cst.p) S.cst.alloc(1);
     if (!S.side) {
         HIP_CHECK(hipStreamCreateWithFlags(&S.side, hipStreamNonBlocking));
@@ -2095,6 +2100,7 @@ void cg_launch_precond(System& S, const CgGrids& g, int precond) {
 bool cg_use_dmf(const System& S) { return S.cgh.colmode && S.dmf.ok; }
 
 #include "bias.inc"
+#include "xrows.inc"
 
 // the data rows' row scales in the matrix-free point order (per solve)
 void cg_dmf_prepare(System& S) {
@@ -2105,9 +2111,18 @@ void cg_dmf_prepare(System& S) {
     if (bias_active(S)) bias_prepare(S);
 }
 
-// the data rows' partials of pᵀNp: Σt² per workgroup, then (biases set) −Σ_j s_j²/D_j
+// the data rows' partials of pᵀNp: Σt² per workgroup, then (biases set) −Σ_j s_j²/D_j, then (extra
+// rows set) their Σt_x² per workgroup
 int cg_nt(const System& S, const CgGrids& g) {
-    return S.cgh.colmode ? g.gD + (bias_active(S) ? S.bias.nbk : 0) : 0;
+    return S.cgh.colmode ? g.gD + (bias_active(S) ? S.bias.nbk : 0) + (xr_active(S) ? S.xr.nbk : 0) : 0;
+}
+
+// extra rows set: t_x = W_x X p and q += Xᵀ W_x t_x, after q = N_s p (and its x-edge correction) and
+// before the node gather whose workgroup 0 sums the partials (xrows.inc)
+void cg_launch_xr(System& S, const CgGrids& g, const double* pnew) {
+    if (!xr_active(S)) return;
+    xr_launch_fwd(S, S.cst.p, nullptr, pnew, 1.0, S.cg_part_t.p + g.gD + (bias_active(S) ? S.bias.nbk : 0));
+    xr_launch_atq(S, S.cst.p, S.cg_q.p);
 }
 
 // biases set: td ← W(I − Q)W A_d p between Ad·p and q += Adᵀ td (bias.inc)
@@ -2216,6 +2231,7 @@ void cg_launch_iteration(System& S, const CgGrids& g, int ph, int precond) {
                            reinterpret_cast<const double4*>(S.dmf_pt.p), pnew, S.cg_t.p, S.cg_part_t.p, g.gD, S.cgd.p,
                            S.cg_coef.p, S.cg_q.p, S.cg_part_g.p + g.gN);
         cg_launch_bias(S, g);
+        cg_launch_xr(S, g, pnew);
         // α in the node gather's workgroup 0 (LSQ_CG_FUSE_ALPHA=0: its own launch)
         static const bool fuse_env = !getenv("LSQ_CG_FUSE_ALPHA") || atoi(getenv("LSQ_CG_FUSE_ALPHA")) != 0;
         const char* rw = getenv("LSQ_CG_ATQ_RW");
@@ -2238,6 +2254,7 @@ void cg_launch_iteration(System& S, const CgGrids& g, int ph, int precond) {
         HIP_CHECK(hipEventRecord(S.ev_join, S.side));
         cg_launch_data(S, g, pold, pnew);
         HIP_CHECK(hipStreamWaitEvent(S.stream, S.ev_join, 0));
+        cg_launch_xr(S, g, pnew);   // after the join: the x-edge pass on S.side also updates q
         cg_launch_atdq(S);
     } else {
         cg_launch_data(S, g, pold, pnew);
@@ -2303,10 +2320,16 @@ void cg_init(System& S, const double* h_b, const double* h_x0, const lsq_opts& o
         // biases set: td ← W(I − Q)W b and ‖r0‖² = bᵀW(I − Q)W b, the reduced problem's
         const int nbk = bias_active(S) ? S.bias.nbk : 0;
         if (nbk) bias_launch_step(S, S.cst.p, S.cg_t.p, S.part_u.p + gi);
+        // extra rows: s0 += Xᵀ W_x² b_x, ‖r0‖² = ‖b‖² += ‖W_x b_x‖²
+        const int nxk = xr_active(S) ? S.xr.nbk : 0;
+        if (nxk) {
+            xr_launch_fwd(S, nullptr, dbp, nullptr, -1.0, S.part_u.p + gi + nbk);
+            xr_launch_atq(S, nullptr, S.cg_s.p);
+        }
         cg_launch_dmf_atq(S, S.cst.p, S.cg_t.p, S.cg_s.p);
         KERNEL_CHECK();
-        hipLaunchKernelGGL(k_cg_init, dim3(1), dim3(BLOCK), 0, st, S.cst.p, S.part_u.p, gi + nbk, S.part_u.p, gi + nbk,
-                           nullptr);
+        hipLaunchKernelGGL(k_cg_init, dim3(1), dim3(BLOCK), 0, st, S.cst.p, S.part_u.p, gi + nbk + nxk, S.part_u.p,
+                           gi + nbk + nxk, nullptr);
     } else {
         // u = W b − A x0 over all rows (Σu² = ‖r0‖²), then s0 = Aᵀu (raw, full space)
         hipLaunchKernelGGL(k_mf_init_u_for(S), dim3(lg.gD + lg.gS), dim3(BLOCK), 0, st, lg.gD, S.mfh.npts, S.Ad.nslices,
@@ -2335,8 +2358,17 @@ void cg_init(System& S, const double* h_b, const double* h_x0, const lsq_opts& o
             cg_launch_dmf_atq(S, S.cst.p, S.cg_t.p, S.cg_s.p);
             KERNEL_CHECK();
         }
-        hipLaunchKernelGGL(k_cg_init, dim3(1), dim3(BLOCK), 0, st, S.cst.p, S.part_u.p, lg.gD + lg.gS + nbk, S.part_b.p,
-                           lg.gD + lg.gS + nbk, nullptr);
+        // extra rows: ‖b‖² += ‖W_x b_x‖², u_x = W_x (b_x − X x0), ‖r0‖² += ‖u_x‖², s0 += Xᵀ W_x u_x
+        const int nxk = xr_active(S) ? S.xr.nbk : 0;
+        if (nxk) {
+            const int nu = lg.gD + lg.gS + nbk;
+            xr_launch_fwd(S, nullptr, dbp, nullptr, -1.0, S.part_b.p + nu);
+            xr_launch_fwd(S, nullptr, dbp, h_x0 ? S.cg_x.p : nullptr, -1.0, S.part_u.p + nu);
+            xr_launch_atq(S, nullptr, S.cg_s.p);
+            KERNEL_CHECK();
+        }
+        hipLaunchKernelGGL(k_cg_init, dim3(1), dim3(BLOCK), 0, st, S.cst.p, S.part_u.p, lg.gD + lg.gS + nbk + nxk,
+                           S.part_b.p, lg.gD + lg.gS + nbk + nxk, nullptr);
     }
     tr.mark(st, "s0 = A'(Wb-Ax0)");
     if (precond == 4) {   // multigrid set-up for these row weights (uses q as scratch)
@@ -2407,6 +2439,7 @@ void cg_kernel_bytes(const System& S, int precond, double out[3]) {
         out[0] = 12.0 * zd + 16.0 * nd + 8.0 * md;
         out[1] = 32.0 * nf + 12.0 * zd + 4.0 * ne + 8.0 * md;
     }
+    if (xr_active(S)) out[0] += xr_step_bytes(S);
     for (const CgVar& V : S.cg_var)   // field-valued parts: fields + p once, q read and written
         out[1] += (double)V.n_eq * 8.0 * V.nfield + 24.0 * (double)V.S0 * V.S1;
     if (precond == 4 && S.mg) {
@@ -2555,6 +2588,7 @@ void cg_profile(System& S, int reps, int precond, double* out) {
             cg_launch_normal(S, g, pold, pnew);
             HIP_CHECK(hipEventRecord(e[1], S.stream));
             cg_launch_data(S, g, pold, pnew);
+            cg_launch_xr(S, g, pnew);
             cg_launch_atdq(S);
             HIP_CHECK(hipEventRecord(e[2], S.stream));
             cg_launch_alpha(S, g);
@@ -2600,6 +2634,7 @@ void cg_profile(System& S, int reps, int precond, double* out) {
             for (int r = 0; r < reps; ++r) {
                 if (k == 0) {
                     cg_launch_data(S, g, S.cg_pb[0].p, S.cg_pb[1].p);
+                    cg_launch_xr(S, g, S.cg_pb[1].p);
                     if (S.cgh.colmode) cg_launch_atdq(S);
                 } else if (k == 1)
                     cg_launch_normal(S, g, S.cg_pb[0].p, S.cg_pb[1].p);
@@ -2624,6 +2659,52 @@ void cg_profile(System& S, int reps, int precond, double* out) {
     out[7] = (cg_use_dmf(S) ? 1.0 : 0.0) + (S.cgh.rw ? 2.0 : 0.0);
     cg_kernel_bytes(S, precond, out + 4);
     S.cg_ready = false;
+}
+
+// The extra rows' two kernels inside real iterations of a live lsq_iterate state (no stop), events
+// between the launches as in cg_profile, so each sees the caches the step's other kernels leave:
+// out4 = {ms k_xr_fwd, ms k_xr_atq (with k_xr_atq_long), ms of the data rows' Ad·p before them, ms of
+// the node gather behind them}, means over reps iterations.
+void cg_profile_xr(System& S, int reps, int precond, double* out) {
+    if (!(S.cg_ready && S.cg_mode == precond))
+        throw std::invalid_argument("lsq_profile_extra_rows: needs the live state of lsq_iterate with this precond");
+    if (!xr_active(S)) throw std::invalid_argument("lsq_profile_extra_rows: no extra rows in the CGNR operator");
+    const CgGrids g = cg_grids(S, precond);
+    std::vector<hipEvent_t> ev(5 * reps);
+    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+    for (int r = 0; r < reps; ++r) {
+        const int par = S.cg_parity;
+        const double* pold = cg_pold(S, par);
+        double* pnew = cg_pnew(S, par);
+        hipEvent_t* e = ev.data() + 5 * r;
+        cg_launch_normal(S, g, pold, pnew);
+        HIP_CHECK(hipEventRecord(e[0], S.stream));
+        cg_launch_data(S, g, pold, pnew);
+        HIP_CHECK(hipEventRecord(e[1], S.stream));
+        xr_launch_fwd(S, S.cst.p, nullptr, pnew, 1.0, S.cg_part_t.p + g.gD + (bias_active(S) ? S.bias.nbk : 0));
+        HIP_CHECK(hipEventRecord(e[2], S.stream));
+        xr_launch_atq(S, S.cst.p, S.cg_q.p);
+        HIP_CHECK(hipEventRecord(e[3], S.stream));
+        cg_launch_atdq(S);
+        HIP_CHECK(hipEventRecord(e[4], S.stream));
+        cg_launch_alpha(S, g);
+        cg_launch_precond(S, g, precond);
+        hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(BLOCK), 0, S.stream, S.cst.p, S.cg_part_r.p, g.gB, 0, nullptr);
+        S.cg_parity = (S.cg_parity + 1) % CG_XK;
+    }
+    HIP_CHECK(hipEventSynchronize(ev.back()));
+    HIP_CHECK(hipStreamSynchronize(S.stream));
+    double t[4] = {0, 0, 0, 0};
+    for (int r = 0; r < reps; ++r) {
+        hipEvent_t* e = ev.data() + 5 * r;
+        float a = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&a, e[1], e[2])); t[0] += a;
+        HIP_CHECK(hipEventElapsedTime(&a, e[2], e[3])); t[1] += a;
+        HIP_CHECK(hipEventElapsedTime(&a, e[0], e[1])); t[2] += a;
+        HIP_CHECK(hipEventElapsedTime(&a, e[3], e[4])); t[3] += a;
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+    for (int k = 0; k < 4; ++k) out[k] = t[k] / reps;
 }
 
 namespace {
@@ -2666,6 +2747,7 @@ void cg_apply_normal(System& S, const double* h_p, double* h_q) {
     if (S.cgh.colmode) {   // q = N_s p, t = Ad p, q += ATd t
         cg_launch_normal(S, g, S.cg_pb[0].p, S.cg_pb[1].p);
         cg_launch_data(S, g, S.cg_pb[0].p, S.cg_pb[1].p);
+        cg_launch_xr(S, g, S.cg_pb[1].p);
         cg_launch_atdq(S);
     } else {
         cg_launch_data(S, g, S.cg_pb[0].p, S.cg_pb[1].p);
@@ -2813,4 +2895,138 @@ std::string bias_refusal(System& S, int method, int precond) {
     if (!cg_available(S, precond)) return "data biases need the structured CGNR operator: " + (S.cg_ok ? S.mg_why : S.cg_why);
     if (!cg_use_dmf(S)) return "data biases need the matrix-free column-mode CGNR data rows (tile mode is not covered)";
     return "";
+}
+
+// ---- extra rows (xrows.inc): formation, column norms, refusals ----------------------------------
+// The staged rows (merged, zero-free, columns ascending, full ids, no removed column: api.hip) on
+// the device: SELL-64 slices, the transpose over the touched columns, and the CSR over the compact
+// columns that ensure_full_csr appends to G.  row0: the system row of the first extra row.
+void xr_form(System& S, int64_t row0) {
+    XrData& X = S.xr;
+    const int64_t m_x = X.st_m, nf = S.mfh.n_full;
+    const int64_t nnz = m_x ? X.st_rp[m_x] : 0;
+    for (int64_t e = 0; e < nnz; ++e)
+        if (X.st_ci[e] < 0 || X.st_ci[e] >= nf)
+            throw std::invalid_argument("lsq_set_matrix_stencil: an extra row's column lies outside [0, n_full)");
+    X.m_x = m_x;
+    X.row0 = row0;
+    X.nnz = nnz;
+    X.on = false;
+    if (!m_x) return;
+    std::vector<int32_t> cmap;
+    if (S.have_colmap) {
+        cmap.resize(nf);
+        S.colmap.download(cmap.data(), nf, S.stream);
+        HIP_CHECK(hipStreamSynchronize(S.stream));
+    }
+    X.h_rp.assign(X.st_rp.begin(), X.st_rp.end());
+    X.h_ci.resize(nnz);
+    X.h_val.assign(X.st_val.begin(), X.st_val.end());
+    for (int64_t e = 0; e < nnz; ++e) X.h_ci[e] = S.have_colmap ? cmap[X.st_ci[e]] : (int32_t)X.st_ci[e];
+    // SELL-64: a slice is as wide as its longest row; padding carries value 0 and column 0
+    const int64_t nsl = (m_x + SELL_C - 1) / SELL_C;
+    std::vector<int64_t> sp(nsl + 1, 0);
+    for (int64_t s = 0; s < nsl; ++s) {
+        int64_t w = 0;
+        for (int64_t r = s * SELL_C; r < std::min(m_x, (s + 1) * SELL_C); ++r) w = std::max(w, X.st_rp[r + 1] - X.st_rp[r]);
+        sp[s + 1] = sp[s] + w * SELL_C;
+    }
+    const int64_t nent = sp[nsl];
+    std::vector<int32_t> sci(std::max<int64_t>(nent, 1), 0);
+    std::vector<double> sval(std::max<int64_t>(nent, 1), 0.0);
+    for (int64_t r = 0; r < m_x; ++r) {
+        const int64_t base = sp[r / SELL_C] + r % SELL_C;
+        for (int64_t e = X.st_rp[r]; e < X.st_rp[r + 1]; ++e) {
+            sci[base + (e - X.st_rp[r]) * SELL_C] = (int32_t)X.st_ci[e];
+            sval[base + (e - X.st_rp[r]) * SELL_C] = X.st_val[e];
+        }
+    }
+    // transpose over the touched columns: rows ascending inside a column (the rows are walked in order)
+    std::vector<int32_t> tc(X.st_ci.begin(), X.st_ci.end());
+    std::sort(tc.begin(), tc.end());
+    tc.erase(std::unique(tc.begin(), tc.end()), tc.end());
+    const int64_t ntc = (int64_t)tc.size();
+    std::vector<int64_t> cp(ntc + 1, 0);
+    std::vector<int32_t> where(std::max<int64_t>(nnz, 1));
+    for (int64_t e = 0; e < nnz; ++e) {
+        where[e] = (int32_t)(std::lower_bound(tc.begin(), tc.end(), (int32_t)X.st_ci[e]) - tc.begin());
+        ++cp[where[e] + 1];
+    }
+    for (int64_t j = 0; j < ntc; ++j) cp[j + 1] += cp[j];
+    std::vector<int64_t> fill(cp.begin(), cp.end() - 1);
+    std::vector<int32_t> cr(std::max<int64_t>(nnz, 1), 0), long_col;
+    std::vector<double> cv(std::max<int64_t>(nnz, 1), 0.0);
+    for (int64_t r = 0; r < m_x; ++r)
+        for (int64_t e = X.st_rp[r]; e < X.st_rp[r + 1]; ++e) {
+            const int64_t k = fill[where[e]]++;
+            cr[k] = (int32_t)r;
+            cv[k] = X.st_val[e];
+        }
+    for (int64_t j = 0; j < ntc; ++j)
+        if (cp[j + 1] - cp[j] > XR_LONG) long_col.push_back((int32_t)j);
+    X.ntc = ntc;
+    X.nlong = (int64_t)long_col.size();
+    X.nbk = grid_for(nsl, BLOCK / 64, XR_NPART);
+    hipStream_t st = S.stream;
+    X.rows.rows = m_x;
+    X.rows.nslices = nsl;
+    X.rows.nent = nent;
+    X.rows.sp.alloc(nsl + 1);
+    X.rows.sp.upload(sp.data(), nsl + 1, st);
+    X.rows.ci.alloc((int64_t)sci.size());
+    X.rows.ci.upload(sci.data(), (int64_t)sci.size(), st);
+    X.rows.val.alloc((int64_t)sval.size());
+    X.rows.val.upload(sval.data(), (int64_t)sval.size(), st);
+    tc.resize(std::max<int64_t>(ntc, 1), 0);
+    X.tc.alloc((int64_t)tc.size());
+    X.tc.upload(tc.data(), (int64_t)tc.size(), st);
+    X.cp.alloc(ntc + 1);
+    X.cp.upload(cp.data(), ntc + 1, st);
+    X.cr.alloc((int64_t)cr.size());
+    X.cr.upload(cr.data(), (int64_t)cr.size(), st);
+    X.cv.alloc((int64_t)cv.size());
+    X.cv.upload(cv.data(), (int64_t)cv.size(), st);
+    long_col.resize(std::max<size_t>(long_col.size(), 1), 0);
+    X.long_col.alloc((int64_t)long_col.size());
+    X.long_col.upload(long_col.data(), (int64_t)long_col.size(), st);
+    X.tblk.alloc(std::max<int64_t>(ntc, 1));
+    X.t.alloc(m_x);
+    X.t.zero(st);
+    HIP_CHECK(hipStreamSynchronize(st));
+    X.dev_bytes = (int64_t)(X.rows.sp.bytes() + X.rows.ci.bytes() + X.rows.val.bytes() + X.tc.bytes() + X.cp.bytes() +
+                            X.cr.bytes() + X.cv.bytes() + X.long_col.bytes() + X.tblk.bytes() + X.t.bytes());
+    // rows that kept no entry still carry b: ‖W_x b_x‖² belongs to ‖b‖ and ‖r0‖ as LSQR on the full
+    // CSR counts it, so they stay on (the kernels then walk empty slices and no touched column)
+    X.on = true;
+}
+
+// norm2 (full space) += the extra rows' squared column norms for the current row scale
+void xr_add_colnorm(System& S, double* norm2_full) {
+    const XrData& X = S.xr;
+    hipLaunchKernelGGL(k_xr_colnorm, dim3(grid_for(X.ntc)), dim3(BLOCK), 0, S.stream, X.ntc, X.tc.p, X.cp.p, X.cr.p,
+                       X.cv.p, S.rs.p + X.row0, norm2_full);
+    KERNEL_CHECK();
+}
+
+// why a solve with extra rows set cannot run (empty: it can)
+std::string xr_refusal(System& S, int method, int precond, int op) {
+    if (!S.xr.m_x) return "";
+    if (S.dist) return "extra rows run on single-GPU handles only";
+    if (method == 1 && precond == 4)
+        return "multigrid (precond 4) does not carry extra rows: its coarse levels would miss their term";
+    if (method == 1 && (precond == 1 || precond == 3) && cg_available(S, precond)) {
+        if (S.xr.on && !S.cgh.colmode) return "extra rows need the column-mode CGNR operator";
+        return "";
+    }
+    if (S.mf && op == 0 && precond != 2 && precond != 5)
+        return "extra rows: LSQR runs on the assembled operator only (op = 1), not the structured stencil operator";
+    return "";
+}
+
+// xr_step_bytes and the device bytes of the extra rows (lsq_extra_rows_info)
+void xr_info(System& S, double* out4) {
+    out4[0] = (double)S.xr.m_x;
+    out4[1] = (double)S.xr.ntc;
+    out4[2] = S.xr.on ? xr_step_bytes(S) : 0.0;
+    out4[3] = (double)S.xr.dev_bytes;
 }

@@ -334,6 +334,38 @@ struct BiasData {
     DBuf<double> bval;              // ID -> bias of the last solve
 };
 
+// Extra sparse rows behind the stencil rows (lsq_set_extra_rows; xrows.inc): ≤ XR_MAXW entries per
+// row, columns = full ids, values unweighted.  Staged on the host before the structured formation,
+// which merges duplicates, drops zeros and the columns the col map removes.  The device keeps the
+// rows as SELL-64 slices and their transpose over the touched columns only (tc: the touched full
+// ids ascending; cp / cr / cv: a CSC with the local row ids ascending inside each column).  Every
+// sum runs in a fixed order without atomics.
+constexpr int XR_MAXW = 32;                 // entries per row after formation
+constexpr int XR_LONG = 64;                 // rows above which a column is summed by a wave of its own
+struct XrData {
+    // staging (lsq_set_extra_rows before the formation)
+    int64_t st_m = 0;
+    std::vector<int64_t> st_rp, st_ci;
+    std::vector<double> st_val;
+    // formed
+    bool on = false;                // rows exist and at least one entry survived
+    int64_t m_x = 0, row0 = 0;      // rows [row0, row0 + m_x) of the system
+    int64_t nnz = 0, ntc = 0, nlong = 0;
+    int nbk = 0;                    // workgroups (= partials of Σ t²) of k_xr_fwd
+    std::vector<int64_t> h_rp;      // the formed rows as CSR over the compact columns (ensure_full_csr)
+    std::vector<int32_t> h_ci;
+    std::vector<double> h_val;
+    Sell rows;                      // column ids = full ids
+    DBuf<int32_t> tc;               // touched full columns, ascending
+    DBuf<int64_t> cp;               // ntc + 1
+    DBuf<int32_t> cr;               // local row of each entry (ascending within a column)
+    DBuf<double> cv;
+    DBuf<int32_t> long_col;         // positions in tc of the columns over XR_LONG rows
+    DBuf<int32_t> tblk;             // touched column -> its column block (block.hip, per factorisation)
+    DBuf<double> t;                 // m_x: rs · X p of the current step
+    int64_t dev_bytes = 0;
+};
+
 struct System {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -462,6 +494,7 @@ struct System {
     DBuf<int32_t> dmf_perm, dmf_cell;   // sorted point -> data row; (y, x) cell -> first sorted point
     std::string cg_why;            // why not (when !cg_ok)
     BiasData bias;                  // eliminated data biases (lsq_set_data_bias; bias.inc)
+    XrData xr;                      // extra sparse rows behind the stencil rows (lsq_set_extra_rows; xrows.inc)
     CgDesc cgh{};
     DBuf<CgDesc> cgd;
     DBuf<double> cg_coef, cg_coefc;  // class-row tables: offset-major (tile mode), group × t (column mode)
@@ -607,6 +640,9 @@ void set_column_blocks_affine(System& S, int64_t nb, int k, const int64_t* base,
 void ensure_blocks(System& S);                     // default structure if none was set
 void block_factor(System& S);                      // R_b⁻¹ for the current row scale
 void block_normal(System& S);                      // (AᵀA)_bb of the system's own rows into blk_Ri
+// lsqr.hip (xrows.inc): the extra rows formed from their staging, and their share of the column norms
+void xr_form(System& S, int64_t row0);
+void xr_add_colnorm(System& S, double* norm2_full);
 void block_factor_in_place(System& S);             // blk_Ri: (AᵀA)_bb -> R_b⁻¹
 void block_factor_packed(int64_t nb, const int64_t* ptr, int kmax, double* Ri, lf_t* Lf,
                          unsigned long long* ndead, hipStream_t st);   // multigrid coarse blocks

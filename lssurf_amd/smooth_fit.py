@@ -13,11 +13,14 @@ valid_data, TOC, R, RMS, timing, E_RMS, dzdt_lags; ``return_fit_objects`` early 
 * everything else (editing, sigma_extra, convergence tests, parse_model) keeps the reference's
   logic on the host.
 
-Options that add columns/rows outside the fd_grid model (sensor grids, jitter, priors,
-lagrangian grids) are outside lssurf_amd's scope and raise NotImplementedError instead of
-silently changing the fit.  Data biases (bias_params) run when the solver key lsq_bias says how:
-'eliminate' (the device eliminates them inside CGNR, lsq_set_data_bias), 'columns' (ordinary
-columns of a generic system) or 'auto'.
+Options that add columns/rows outside the fd_grid model (sensor grids, jitter, lagrangian grids)
+are outside lssurf_amd's scope and raise NotImplementedError instead of silently changing the fit.
+The dz priors (prior_args, prior_edge_args; match_priors.py) take in-memory grids; their rows stay
+last in Gc and the device carries them as extra rows inside matrix-free CGNR (lsq_set_extra_rows).
+With priors compute_E, n_gpus > 1 and lsq_bias='eliminate' raise NotImplementedError.
+Data biases (bias_params) run when the solver key lsq_bias says how: 'eliminate' (the device
+eliminates them inside CGNR, lsq_set_data_bias), 'columns' (ordinary columns of a generic system)
+or 'auto' (with priors: 'columns', with a warning where it would have eliminated).
 """
 from time import ctime, time
 
@@ -34,7 +37,8 @@ from .grid_functions import setup_averaging_ops, setup_avg_mask_ops, setup_grids
     validate_by_dz_mask
 from .lin_op import known_range, lin_op, toc_range
 from ._native import NativeError
-from .assemble import describe
+from .assemble import describe, extra_rows_of
+from .match_priors import match_prior_dz, match_tile_edges
 from .solver import LSQSolver
 
 DEFAULTS = {'reference_epoch': 0, 'W_ctr': 1e4, 'return_fit_objects': False, 'mask_file': None,
@@ -58,7 +62,7 @@ DEFAULTS = {'reference_epoch': 0, 'W_ctr': 1e4, 'return_fit_objects': False, 'ma
             # data biases (bias_params): None refuses them; 'eliminate', 'columns' or 'auto'
             'lsq_bias': None}
 
-OUT_OF_SCOPE = ('sensor_grid_bias_params', 'prior_args', 'prior_edge_args', 'lagrangian_coords',
+OUT_OF_SCOPE = ('sensor_grid_bias_params', 'lagrangian_coords',
                 'constraint_scaling_maps', 'mask_file', 'bias_edit_vals')
 
 
@@ -66,23 +70,71 @@ class FitSystem:
     """The device-resident smooth_fit system: G = [G_data; Gc] (unweighted COO -> device CSR),
     Ip_c as a column map; rows re-weighted / re-selected per outer iteration."""
 
-    def __init__(self, G_data, Gc, keep_cols, n_full, device=0, structured=True, grids=None, bias=None):
+    def __init__(self, G_data, Gc, keep_cols, n_full, device=0, structured=True, grids=None, bias=None,
+                 extra_ops=None, extra_csr=None):
         """bias = (ids, c): eliminated data biases (LSQSolver.set_data_bias) — G_data and Gc are then
         the grid-only operators, the caller's row weights and rhs may carry further (bias
-        constraint) rows behind them, and the biases take the columns after n_full in expand()."""
+        constraint) rows behind them, and the biases take the columns after n_full in expand().
+        extra_ops: the operators behind Gc's last rows that are neither interpolation nor stencil
+        rows (the priors of match_priors).  With a structured description of the other rows they
+        are staged as the device's extra rows (LSQSolver.set_extra_rows) and matrix-free CGNR
+        carries them; if the device refuses, the whole system takes the COO path.
+        extra_csr = (indptr, cols_full, vals): extra rows that are not in Gc at all, behind its last
+        row (the row weights, mask and rhs of solve() then have n_data + Gc.N_eq + their count
+        entries); they need the structured formation."""
         self.n_data, self.n_con = int(G_data.N_eq), int(Gc.N_eq)
         self.keep_cols = keep_cols
         self.n_full = int(n_full)
         self.solver = LSQSolver(device)
         self.solver.set_col_map(self.n_full, keep_cols)
         m = self.n_data + self.n_con
-        desc = describe(G_data, Gc, with_fields=True) if structured else None
-        self.desc = desc           # the descriptors (bench.py's structured CPU baseline reads them)
-        self.formation = 'stencil' if desc is not None else 'coo'
+        extra_ops = list(extra_ops or [])
+        n_extra = sum(int(op.N_eq) for op in extra_ops)
+        if n_extra and extra_rows_of(Gc) != n_extra:
+            raise ValueError('FitSystem: extra_ops must be the last rows of Gc')
+        if extra_csr is not None:
+            if n_extra or not structured:
+                raise ValueError('FitSystem: extra_csr goes with the structured formation and without extra_ops')
+            n_extra = int(np.size(extra_csr[0])) - 1
+            self.n_con += n_extra  # constraint rows as solve() counts them
+            m += n_extra
+        desc = describe(G_data, Gc, with_fields=True, extra_rows=n_extra > 0) if structured else None
+        if extra_csr is not None and desc is None:
+            raise ValueError('FitSystem: extra_csr needs a structured description of G_data and Gc')
+        self.n_extra = 0           # rows the device holds as extra rows
         if desc is not None:       # rows generated on the device from the grids and stencils
             gdesc, interp, coords, stencils, npts, fields = desc
-            self.solver.set_matrix_stencil(m, self.n_full, gdesc, interp, coords, stencils, npts, fields=fields)
-        else:                      # generic lin_op: host triplets -> device CSR
+            # Only a refusal of the extra rows themselves leads to the COO path, and it says so: at staging
+            # (e.g. > 32 entries in one row), or at formation when the other rows did not come out
+            # matrix-free ('extra rows need …').  Any other formation error stays an error.
+            try:
+                if n_extra:        # staged first: they become the last rows of the formation
+                    self.solver.set_extra_rows(*(extra_csr if extra_csr is not None else _extra_rows_csr(extra_ops)))
+                refusal = None
+            except NativeError as e:
+                if extra_csr is not None:
+                    raise
+                refusal = e
+            if refusal is None:
+                try:
+                    self.solver.set_matrix_stencil(m, self.n_full, gdesc, interp, coords, stencils, npts,
+                                                   fields=fields)
+                    self.n_extra = n_extra
+                except NativeError as e:
+                    if not n_extra or extra_csr is not None or 'extra rows need' not in str(e):
+                        raise
+                    refusal = e
+            if refusal is not None:
+                warnings.warn(f'FitSystem: the device refuses the {n_extra} extra rows ({refusal}); the whole '
+                              f'system is formed from triplets (COO) and loses matrix-free CGNR',
+                              RuntimeWarning, stacklevel=2)
+                self.solver.close()   # a fresh handle: nothing staged, nothing half formed
+                self.solver = LSQSolver(device)
+                self.solver.set_col_map(self.n_full, keep_cols)
+                desc = None
+        self.desc = desc           # the descriptors (bench.py's structured CPU baseline reads them)
+        self.formation = 'stencil' if desc is not None else 'coo'
+        if desc is None:           # generic lin_op: host triplets -> device CSR
             r1, c1, v1 = G_data.triplets()
             r2, c2, v2 = Gc.triplets()
             self.solver.set_matrix_coo(m, self.n_full, np.concatenate([r1, r2 + self.n_data]),
@@ -103,7 +155,9 @@ class FitSystem:
                     self.solver.set_column_blocks_csr(*blocks)
                     self.has_blocks = True
                     self._blocks = blocks
-        self._mg = None            # multigrid (precond 4) availability, probed on first use
+        # multigrid (precond 4) availability, probed on first use; never with extra rows: the coarse
+        # levels would not carry their term, so 'auto' takes block-Jacobi as with eliminated biases
+        self._mg = False if self.n_extra else None
         self.mg_build_s = 0.0
         self.stats = None
         self.bias_ids, self.bias_vals = None, None
@@ -191,6 +245,23 @@ class FitSystem:
 
     def close(self):
         self.solver.close()
+
+
+def _extra_rows_csr(ops):
+    """(indptr, cols, vals) of the stacked operators' triplets, rows in order, a row's entries in
+    the order of the triplets (the device sums duplicates in that order)."""
+    rr, cc, vv, row0 = [], [], [], 0
+    for op in ops:
+        r, c, v = op.triplets()
+        rr.append(np.ravel(r) + row0)
+        cc.append(np.ravel(c))
+        vv.append(np.ravel(v))
+        row0 += int(op.N_eq)
+    r, c, v = np.concatenate(rr), np.concatenate(cc), np.concatenate(vv)
+    order = np.argsort(r, kind='stable')
+    indptr = np.zeros(row0 + 1, dtype=np.int64)
+    np.cumsum(np.bincount(r, minlength=row0), out=indptr[1:])
+    return indptr, c[order].astype(np.int64), v[order].astype(np.float64)
 
 
 def check_data_against_DEM(in_TSE, data, m0, G_data, DEM_tol):
@@ -531,19 +602,29 @@ def parse_model(m, m0, data, R, RMS, G_data, averaging_ops, Gc, Ec, grids, args,
                           np.sqrt(sums['notide_scaled'][cols].reshape(shape) / m[ff].count)})
 
 
-def _bias_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, bias_model, mode, grids, device, args):
+def _bias_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, bias_model, mode, grids, device, args,
+                     prior_ops=()):
     """The device system of a fit with data biases.  'eliminate': the grid-only operators on the
     device plus lsq_set_data_bias (the bias constraint rows are the last rows of Gc, so the device
     rows are a prefix of the host rows); 'columns': the biases as ordinary columns of a generic
     (COO-formed) system; 'auto': 'columns' when the grid unknowns (the eliminating system's columns)
     are few enough for the dense preconditioner, when the options ask for what only 'columns' runs
     (LSQR, the dense preconditioner) or when the device cannot eliminate (no matrix-free data rows),
-    else 'eliminate'."""
+    else 'eliminate'.
+    With prior_ops (the priors behind the bias constraint rows of Gc) only 'columns' runs: the device
+    rows of 'eliminate' are a prefix of the host rows, which rows behind the bias constraints would
+    break.  smooth_fit refuses 'eliminate' with priors; 'auto' takes 'columns' and warns where it
+    would have eliminated, since the generic system costs the memory and speed of matrix-free CGNR."""
     n_grid = G_grid.col_N if G_grid is not None else None
     n_bias = int(G_data.col_N) - int(n_grid) if n_grid is not None else 0
     if mode == 'auto' and (describe(G_grid, Gc_grid, with_fields=True) is None or
                            np.count_nonzero(keep_cols < n_grid) <= args['lsq_dense_max'] or
                            args['lsq_method'] == 'lsqr' or args['lsq_precond'] == 2):
+        mode = 'columns'
+    if prior_ops and mode != 'columns':
+        warnings.warn("smooth_fit: lsq_bias='auto' with prior_args / prior_edge_args takes 'columns': biases and "
+                      "priors together run as a generic (COO-formed) system, not matrix-free CGNR",
+                      RuntimeWarning, stacklevel=3)
         mode = 'columns'
     if mode != 'columns':
         ids = np.asarray(data.bias_ID).astype(np.int32)
@@ -586,6 +667,17 @@ def smooth_fit(**kwargs):
         if bias_mode == 'eliminate' and args['lsq_precond'] not in ('auto', 1, 3, 4):
             raise NotImplementedError("smooth_fit: lsq_bias='eliminate' runs CGNR with lsq_precond 'auto', 1, 3 or "
                                       "4; the dense preconditioner needs lsq_bias='columns'")
+
+    has_priors = args.get('prior_args') is not None or args.get('prior_edge_args') is not None
+    if has_priors:
+        # priors (match_priors): rows behind the constraints that the device carries as extra rows
+        if args['compute_E']:
+            raise NotImplementedError("smooth_fit: compute_E with prior_args / prior_edge_args is outside lssurf_amd")
+        if int(args['n_gpus']) > 1 or (args['devices'] is not None and len(args['devices']) > 1):
+            raise NotImplementedError("smooth_fit: prior_args / prior_edge_args run on one GPU")
+        if args['bias_params'] is not None and bias_mode == 'eliminate':
+            raise NotImplementedError("smooth_fit: priors with lsq_bias='eliminate' are outside lssurf_amd; "
+                                      "lsq_bias='columns' (or 'auto') carries both")
 
     valid_data = np.isfinite(args['data'].z)
     if 'sensor' not in args['data'].fields:
@@ -647,6 +739,17 @@ def smooth_fit(**kwargs):
         zero_prior.add(constraint_op_list[-1].name)
         if args['bias_nsigma_edit']:
             bias_model['bias_param_dict']['edited'] = np.zeros_like(bias_model['bias_param_dict']['ID'], dtype=bool)
+    # priors, in the reference's order (smooth_fit.py:575-582), behind every other constraint
+    prior_ops = []
+    if args.get('prior_args') is not None:
+        prior_ops += match_prior_dz(grids, **args['prior_args'])
+    if args.get('prior_edge_args') is not None:
+        edge_ops, _ = match_tile_edges(grids, args['reference_epoch'], **args['prior_edge_args'])
+        prior_ops += edge_ops
+        if args['VERBOSE']:
+            print(f'smooth_fit: found prior constraints in {len(edge_ops)} tiles')
+    constraint_op_list += prior_ops
+    prior_names = {op.name for op in prior_ops}
     Gc = lin_op(None, name='constraints').vstack(constraint_op_list)
     N_eq = G_data.N_eq + Gc.N_eq
     Ed = data.sigma.ravel()
@@ -664,6 +767,7 @@ def smooth_fit(**kwargs):
     rhs = np.zeros([N_eq])
     rhs[0:data.size] = data.z.ravel()
     b_rows = data.size   # rhs[b_rows:] == 0: only the data rows (and non-zero priors) cross PCIe
+    b_rows_all = None    # the same with the prior ops counted (systems that hold them as ordinary rows)
     for op in constraint_op_list:   # rhs[data.size:] = the concatenated priors
         if op.name not in zero_prior:
             rows = _toc_slice(Gc, op.name)
@@ -675,14 +779,18 @@ def smooth_fit(**kwargs):
                 rhs[data.size + rows] = prior
                 end = int(np.max(rows)) + 1 if np.size(rows) else 0
             if np.any(prior != 0):
-                b_rows = max(b_rows, data.size + end)
+                if op.name in prior_names:   # the device uploads its extra rows' b itself
+                    b_rows_all = max(b_rows_all or 0, data.size + end)
+                else:
+                    b_rows = max(b_rows, data.size + end)
     keep_cols = reference_epoch_keep_cols(G_data.col_N, grids['dz'], args['reference_epoch'])
     timing['setup'] = time() - tic
     in_TSE = data.three_sigma_edit > 0.01 if 'three_sigma_edit' in data.fields else np.ones(G_data.N_eq, dtype=bool)
     if args['VERBOSE']:
         print('initial: %d:' % np.max(G_data.r), flush=True)
     if args['return_fit_objects']:
-        return {'data': data, 'G_data': G_data, 'Gc': Gc, 'grids': grids, 'Ed': Ed, 'Ec': Ec()}
+        return {'data': data, 'G_data': G_data, 'Gc': Gc, 'grids': grids, 'Ed': Ed, 'Ec': Ec(),
+                'prior_ops': prior_ops, 'rhs': rhs}
 
     system = None
     try:
@@ -698,11 +806,16 @@ def smooth_fit(**kwargs):
                                   'sharing one device; see INTEGRATION.md §5', RuntimeWarning, stacklevel=2)
                 system = MultiDeviceFitSystem(G_data, Gc, keep_cols, Gc.col_N, devices)
             elif bias_model:
-                system = _bias_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, bias_model, bias_mode, grids,
-                                          devices[0], args)
+                system = _bias_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, bias_model,
+                                          bias_mode, grids, devices[0], args, prior_ops=prior_ops)
             else:
-                system = FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=devices[0], grids=grids)
+                system = FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=devices[0], grids=grids,
+                                   extra_ops=prior_ops)
+            if b_rows_all is not None and not getattr(system, 'n_extra', 0):
+                b_rows = max(b_rows, b_rows_all)
             system.b_rows = b_rows
+            timing['formation'] = getattr(system, 'formation', None)   # 'stencil' or 'coo'
+            timing['extra_rows'] = int(getattr(system, 'n_extra', 0))  # prior rows the device holds as extra rows
             timing['device_setup'] = time() - tic
             tic_iteration = time()
             m0, sigma_extra, in_TSE, rs_data = iterate_fit(data, system, rhs, TCinv_diag, G_data, Gc, in_TSE,

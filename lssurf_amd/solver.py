@@ -93,6 +93,31 @@ class LSQSolver:
             self.n = int(n_full)
         self.n_full = int(n_full)
 
+    def set_extra_rows(self, indptr, cols_full, vals):
+        """Extra sparse rows behind the stencil rows (lsq_set_extra_rows), staged before
+        set_matrix_stencil: a CSR over the full column space, at most 32 entries per row after
+        duplicates are summed and zeros and removed columns dropped.  indptr = None clears."""
+        if indptr is None or np.size(indptr) <= 1:
+            self._check(self._L.lsq_set_extra_rows(self._h, 0, None, None, None), 'lsq_set_extra_rows')
+            return
+        indptr, cols_full = as_c(indptr, np.int64), as_c(cols_full, np.int64)
+        vals = as_c(vals, np.float64)
+        self._check(self._L.lsq_set_extra_rows(self._h, indptr.size - 1, ptr(indptr), ptr(cols_full), ptr(vals)),
+                    'lsq_set_extra_rows')
+
+    def extra_rows_info(self):
+        """{rows, touched columns, step bytes (xr_step_bytes), device bytes} of the extra rows."""
+        o = np.zeros(4)
+        self._check(self._L.lsq_extra_rows_info(self._h, ptr(o)), 'lsq_extra_rows_info')
+        return {'m_x': int(o[0]), 'touched_cols': int(o[1]), 'step_bytes': float(o[2]), 'device_bytes': int(o[3])}
+
+    def profile_extra_rows(self, reps=20, precond=3):
+        """Device time (ms) of the extra rows' kernels inside real iterations (after iterate() with the
+        same precond), with the data rows' Ad·p before them and the node gather behind them."""
+        o = np.zeros(4)
+        self._check(self._L.lsq_profile_extra_rows(self._h, int(reps), int(precond), ptr(o)), 'lsq_profile_extra_rows')
+        return dict(zip(['k_xr_fwd', 'k_xr_atq', 'data_fwd', 'node_gather'], o.tolist()))
+
     def set_row_weight(self, w):
         w = None if w is None else as_c(w, np.float64)
         self._check(self._L.lsq_set_row_weight(self._h, ptr(w)), 'lsq_set_row_weight')
