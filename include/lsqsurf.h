@@ -169,11 +169,26 @@ int lsq_set_stencil_fields(lsq_handle* h, int32_t stencil, int32_t ntpl, const i
  * Matrix-free CGNR (method 1) carries them with precond 1 or 3: the normal operator gains
  * XᵀW_x²X (two small kernels per step, bitwise reproducible), the Jacobi norms and the node-block
  * factors gain the same sums, and lsq_normal_apply includes the term.  With lsq_opts.b_rows the
- * library also uploads b[m − m_x, m).  Refused with −2 and the reason: precond 4 (the multigrid's
- * coarse levels would miss the term; lsq_cg_available(h, 4) reports 0), LSQR on the structured
- * stencil operator (op = 0 on a lazily formed system), tile-mode CGNR, and every distributed,
- * virtual or device-group rank (the formation itself is refused there).  May be combined with
- * lsq_set_data_bias: the two terms are independent.
+ * library also uploads b[m − m_x, m).  Refused with −2 and the reason: precond 4 unless the rows
+ * are lumped (below; without it the multigrid's coarse levels would miss the term and
+ * lsq_cg_available(h, 4) reports 0), LSQR on the structured stencil operator (op = 0 on a lazily
+ * formed system), tile-mode CGNR, and every distributed, virtual or device-group rank (the
+ * formation itself is refused there).  May be combined with lsq_set_data_bias: the two terms are
+ * independent.
+ * lsq_set_extra_rows_lumping(h, 1), after the rows are staged and before lsq_set_matrix_stencil
+ * (cleared with the staging): precond 4 carries the rows.  Level 0 of the V-cycle applies XᵀW_x²X
+ * exactly; on the coarse levels each row is lumped into the node blocks like a data row: with
+ * τ_s = Σ_n x[n, s] and the (y, x) weights ω_n = Σ_s |x[n, s]| / Σ |x| (a separable row w ⊗ τ, w ≥ 0,
+ * Σ w = 1 gives back w and τ), level 1 gains B_1[m] += rs² (Σ_n P[n, m] ω_n) τ τᵀ, restricted to the
+ * levels below with the data rows' blocks, on every solve whose weights or mask changed, in a fixed
+ * order without atomics.  A row is lumpable when its dz entries lie in at most two adjacent epochs
+ * (the z0 entry is free).  Still refused with −2 and the reason: a row that is not lumpable (named
+ * in the reason), the z0-refined hierarchy, tile-mode CGNR, distributed / virtual / group ranks.
+ * Without the call nothing changes.
+ * lsq_extra_rows_mg_info: out4 = {rows lumped, touched level-1 nodes, algorithmic bytes of one
+ * lumping pass, device bytes of its tables}; zeros when precond 4 does not carry the rows.
+ * lsq_profile_extra_rows_lumping: reps lumping passes of the set-up with device events between the
+ * kernels: out2 = {ms of the extra rows' pass, ms of the data rows' k_mg_lump1 before it}.
  * lsq_extra_rows_info: out4 = {m_x, touched columns, algorithmic bytes of one CG step's two
  * kernels, device bytes of the rows and their transpose}.
  * lsq_profile_extra_rows: after lsq_iterate with the same precond (its live state), runs reps more
@@ -181,7 +196,10 @@ int lsq_set_stencil_fields(lsq_handle* h, int32_t stencil, int32_t ntpl, const i
  * long-column kernel), ms of the data rows' Ad·p before them, ms of the node gather behind them}. */
 int lsq_set_extra_rows(lsq_handle* h, int64_t m_x, const int64_t* indptr, const int64_t* cols_full,
                        const double* vals);
+int lsq_set_extra_rows_lumping(lsq_handle* h, int32_t on);
 int lsq_extra_rows_info(lsq_handle* h, double* out4);
+int lsq_extra_rows_mg_info(lsq_handle* h, double* out4);
+int lsq_profile_extra_rows_lumping(lsq_handle* h, int32_t reps, double* out2);
 int lsq_profile_extra_rows(lsq_handle* h, int32_t reps, int32_t precond, double* out4);
 
 /* Replace the row weights (TCinv of iterate_fit, smooth_fit.py:123-129) without re-forming. */

@@ -51,6 +51,7 @@ class LsqStats(ctypes.Structure):
 # every symbol declared in include/lsqsurf.h
 EXPORTS = ['lsq_default_opts', 'lsq_create', 'lsq_destroy', 'lsq_last_error', 'lsq_set_col_map',
            'lsq_set_matrix_coo', 'lsq_set_matrix_stencil', 'lsq_set_stencil_fields', 'lsq_set_extra_rows', 'lsq_extra_rows_info',
+           'lsq_set_extra_rows_lumping', 'lsq_extra_rows_mg_info', 'lsq_profile_extra_rows_lumping',
            'lsq_profile_extra_rows', 'lsq_set_row_weight',
            'lsq_set_row_mask',
            'lsq_set_column_blocks', 'lsq_set_column_blocks_affine', 'lsq_shape', 'lsq_get_csr', 'lsq_release_full_csr',
@@ -107,6 +108,9 @@ def load():
         'lsq_set_data_bias': ([P, i64, P, i64, P], ctypes.c_int),
         'lsq_set_extra_rows': ([P, i64, P, P, P], ctypes.c_int),
         'lsq_extra_rows_info': ([P, P], ctypes.c_int),
+        'lsq_set_extra_rows_lumping': ([P, i32], ctypes.c_int),
+        'lsq_extra_rows_mg_info': ([P, P], ctypes.c_int),
+        'lsq_profile_extra_rows_lumping': ([P, i32, P], ctypes.c_int),
         'lsq_profile_extra_rows': ([P, i32, i32, P], ctypes.c_int),
         'lsq_get_data_bias': ([P, P], ctypes.c_int),
         'lsq_sell_info': ([P, P], ctypes.c_int),

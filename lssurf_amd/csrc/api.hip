@@ -23,6 +23,8 @@ void bias_get(System& S, double* h_b);
 std::string bias_refusal(System& S, int method, int precond);
 std::string xr_refusal(System& S, int method, int precond, int op);
 void xr_info(System& S, double* out4);
+void xr_mg_info(System& S, double* out4);
+void mg_profile_lump_xr(System& S, int reps, double* out2);
 int lsqr_iterate(System& S, const double* h_b, int64_t iters, const lsq_opts& o, lsq_stats* stats);
 void lsqr_profile(System& S, int reps, int op, double* out);
 void lsqr_sigma_x(System& S, double* h_E);
@@ -209,6 +211,7 @@ int lsq_set_extra_rows(lsq_handle* h, int64_t m_x, const int64_t* indptr, const 
         lsq::XrData& X = S.xr;
         if (m_x <= 0 || !indptr) {   // clears the staging
             X.st_m = 0;
+            X.st_lump = false;
             X.st_rp.clear();
             X.st_ci.clear();
             X.st_val.clear();
@@ -256,6 +259,35 @@ int lsq_set_extra_rows(lsq_handle* h, int64_t m_x, const int64_t* indptr, const 
         X.st_rp = std::move(rp);
         X.st_ci = std::move(ci);
         X.st_val = std::move(val);
+        return 0;
+    });
+}
+
+int lsq_set_extra_rows_lumping(lsq_handle* h, int32_t on) {
+    return guarded(h, [&](lsq::System& S) {
+        if (S.G.rp.p) return fail(S, "lsq_set_extra_rows_lumping must precede lsq_set_matrix_stencil");
+        if (on && S.xr.st_m <= 0) return fail(S, "lsq_set_extra_rows_lumping: no extra rows staged");
+        S.xr.st_lump = on != 0;
+        return 0;
+    });
+}
+
+int lsq_extra_rows_mg_info(lsq_handle* h, double* out4) {
+    return guarded(h, [&](lsq::System& S) {
+        if (!S.G.rp.p) return fail(S, "lsq_extra_rows_mg_info: no matrix");
+        if (!out4) return fail(S, "lsq_extra_rows_mg_info: null output");
+        lsq::xr_mg_info(S, out4);
+        return 0;
+    });
+}
+
+int lsq_profile_extra_rows_lumping(lsq_handle* h, int32_t reps, double* out2) {
+    return guarded(h, [&](lsq::System& S) {
+        if (!S.G.rp.p) return fail(S, "lsq_profile_extra_rows_lumping: no matrix");
+        if (!out2) return fail(S, "lsq_profile_extra_rows_lumping: null output");
+        if (S.dist) return fail(S, "lsq_profile_extra_rows_lumping: single-GPU handles only");
+        lsq::graph_cache_drop(&S);
+        lsq::mg_profile_lump_xr(S, reps > 0 ? reps : 10, out2);
         return 0;
     });
 }
@@ -453,9 +485,12 @@ int lsq_cg_available(lsq_handle* h, int32_t precond) {
                 return 0;
             }
         }
-        if (S.xr.m_x && precond == 4) {   // the coarse levels would not carry the extra rows' term
-            S.err = lsq::xr_refusal(S, 1, 4, 0);
-            return 0;
+        if (S.xr.m_x && precond == 4) {   // only lumped rows reach the coarse levels (lsq_set_extra_rows_lumping)
+            const std::string why = lsq::xr_refusal(S, 1, 4, 0);
+            if (!why.empty()) {
+                S.err = why;
+                return 0;
+            }
         }
         if (lsq::cg_available(S, precond)) {
             if (S.xr.m_x) {

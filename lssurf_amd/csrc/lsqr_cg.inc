@@ -2707,6 +2707,37 @@ void cg_profile_xr(System& S, int reps, int precond, double* out) {
     for (int k = 0; k < 4; ++k) out[k] = t[k] / reps;
 }
 
+// The lumping pass of the multigrid set-up in place (lsq_profile_extra_rows_lumping): reps times the
+// level-1 blocks of the data rows (k_mg_lump1) and then the extra rows' share (k_mg_lump_xr and its
+// long-node kernel), events between them: out2 = {ms of the extra rows' pass, ms of k_mg_lump1}.
+// B_1 ends as a set-up leaves it.
+void mg_profile_lump_xr(System& S, int reps, double* out2) {
+    if (!cg_available(S, 4) || !S.mg || !xr_lumped(S))
+        throw std::invalid_argument("lsq_profile_extra_rows_lumping: the multigrid does not carry lumped extra rows");
+    cg_workspace(S);
+    cg_dmf_prepare(S);
+    std::vector<hipEvent_t> ev(3 * reps);
+    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+    for (int r = 0; r < reps; ++r) {
+        HIP_CHECK(hipEventRecord(ev[3 * r], S.stream));
+        mg_setup_lump1(S);
+        HIP_CHECK(hipEventRecord(ev[3 * r + 1], S.stream));
+        mg_setup_lump_xr(S);
+        HIP_CHECK(hipEventRecord(ev[3 * r + 2], S.stream));
+    }
+    HIP_CHECK(hipStreamSynchronize(S.stream));
+    double t[2] = {0, 0};
+    for (int r = 0; r < reps; ++r) {
+        float a = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&a, ev[3 * r + 1], ev[3 * r + 2])); t[0] += a;
+        HIP_CHECK(hipEventElapsedTime(&a, ev[3 * r], ev[3 * r + 1])); t[1] += a;
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+    out2[0] = t[0] / reps;
+    out2[1] = t[1] / reps;
+    S.cg_ready = false;
+}
+
 namespace {
 __global__ __launch_bounds__(BLOCK) void k_perm_gather(int64_t n, const int32_t* __restrict__ perm,
                                                        const double* __restrict__ src, double* __restrict__ dst) {
@@ -2912,6 +2943,10 @@ void xr_form(System& S, int64_t row0) {
     X.row0 = row0;
     X.nnz = nnz;
     X.on = false;
+    X.lump_req = m_x > 0 && X.st_lump;   // the tables follow with the hierarchy (mg.inc, xr_lump_prepare)
+    X.lump_built = X.lump_ok = false;
+    X.lump_why.clear();
+    X.l_rows = X.l_nodes = X.l_ent = X.l_long = X.l_dev_bytes = 0;
     if (!m_x) return;
     std::vector<int32_t> cmap;
     if (S.have_colmap) {
@@ -3012,8 +3047,21 @@ void xr_add_colnorm(System& S, double* norm2_full) {
 std::string xr_refusal(System& S, int method, int precond, int op) {
     if (!S.xr.m_x) return "";
     if (S.dist) return "extra rows run on single-GPU handles only";
-    if (method == 1 && precond == 4)
-        return "multigrid (precond 4) does not carry extra rows: its coarse levels would miss their term";
+    if (method == 1 && precond == 4) {
+        if (!S.xr.lump_req)
+            return "multigrid (precond 4) does not carry extra rows: its coarse levels would miss their term";
+        // lumping requested (lsq_set_extra_rows_lumping): the hierarchy carries them when every row fits
+        // a node block and level 0 is the shared-lattice column-mode operator
+        if (!cg_available(S, 4)) return "";   // the caller reports why there is no hierarchy
+        if (S.mg->mixed)
+            return "multigrid (precond 4) with lumped extra rows: the z0-refined hierarchy does not carry them";
+        if (S.xr.on && !S.cgh.colmode)
+            return "multigrid (precond 4) with lumped extra rows needs the column-mode CGNR operator";
+        if (!S.xr.lump_ok)
+            return "multigrid (precond 4): the extra rows cannot be lumped: " +
+                   (S.xr.lump_why.empty() ? std::string("no tables for this hierarchy") : S.xr.lump_why);
+        return "";
+    }
     if (method == 1 && (precond == 1 || precond == 3) && cg_available(S, precond)) {
         if (S.xr.on && !S.cgh.colmode) return "extra rows need the column-mode CGNR operator";
         return "";
@@ -3021,6 +3069,18 @@ std::string xr_refusal(System& S, int method, int precond, int op) {
     if (S.mf && op == 0 && precond != 2 && precond != 5)
         return "extra rows: LSQR runs on the assembled operator only (op = 1), not the structured stencil operator";
     return "";
+}
+
+// lsq_extra_rows_mg_info: {lumped rows, touched level-1 nodes, algorithmic bytes of one lumping
+// pass, device bytes of its tables}; zeros when the rows are not lumped
+void xr_mg_info(System& S, double* out4) {
+    out4[0] = out4[1] = out4[2] = out4[3] = 0.0;
+    if (!S.xr.m_x || !S.xr.lump_req || S.dist) return;
+    if (!cg_available(S, 4) || !S.mg || !S.xr.lump_ok) return;
+    out4[0] = (double)S.xr.l_rows;
+    out4[1] = (double)S.xr.l_nodes;
+    out4[2] = xr_lump_bytes(S);
+    out4[3] = (double)S.xr.l_dev_bytes;
 }
 
 // xr_step_bytes and the device bytes of the extra rows (lsq_extra_rows_info)

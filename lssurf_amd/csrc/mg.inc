@@ -20,6 +20,9 @@
 //                  the level-ℓ interpolation, so B_ℓ is the row-sum lumping of its Galerkin data
 //                  term; prototype: 36 vs 32 iterations with the exact term).  B_ℓ is an arrow +
 //                  tridiagonal (t) block: 3·nt doubles per node.
+//   extra rows   — (lsq_set_extra_rows_lumping) exact on level 0 (k_xr_fwd / k_xr_atq); below, each
+//                  row is a (y, x) weight times a τ with a z0 entry and two adjacent epochs, lumped
+//                  into B_1 like a data row (k_mg_lump_xr) and restricted with it.
 // Smoother: Chebyshev of degree MG_DEG0 (level 0) / MG_DEG (coarse levels) on M_ℓ⁻¹N_ℓ, M_ℓ = the per-node blocks of N_ℓ (level 0:
 // the block-Jacobi factors of precond 3, fp32 R_b⁻¹), interval [λ/10, 1.1 λ] with λ the Rayleigh
 // quotient of MG_POW power steps in the M inner product.  Coarsest level (≤ MG_COARSE nodes per
@@ -134,6 +137,7 @@ struct MgHier {
     DBuf<double> scal;           // op-kernel β (power steps: scale − 1; V-cycle: 0)
     DBuf<CgState> mst;           // stop = 0: the set-up ops run regardless of the solve's state
     DBuf<double> part1, part2, part_t;
+    DBuf<double> part_x;         // level 0 with lumped extra rows: k_xr_fwd's partials (scratch)
     DBuf<double> d0, res0;       // level-0 Chebyshev direction and residual
     bool var = false;            // field-valued z0 parts (k_cg_var2d on level 0, MgLevel::vz below)
     DBuf<double> part_v;         // their level-0 partials (scratch)
@@ -483,6 +487,90 @@ __global__ __launch_bounds__(64) void k_mg_lump1(DmfDesc D, const int32_t* __res
         }
         for (int k = 0; k < nbB; ++k) B[((int64_t)a * S1c + b) * nbB + k] = LA[k * 64 + lane];
     }
+}
+
+// The extra rows' share of the level-1 blocks (lsq_set_extra_rows_lumping; xr_lump.hpp): a row is a
+// (y, x) weight times an epoch vector τ with a z0 entry and at most two adjacent epochs (t, t + 1),
+// i.e. a data row with its own τ_z, so it lumps into the same layout:
+//   B[m] += Σ_r rs_r² w¹_{m,r} · [τ_z², τ_z τ_t, τ_t², τ_t τ_{t+1}]
+// over the transpose of the touched level-1 nodes (rows ascending inside a node).  Launched after
+// k_mg_lump1 wrote B; k_mg_restrict_b then carries the sum to the levels below.  One row's share of
+// node accumulators acc[entry · 64 + lane] in LDS (the epoch varies per row):
+__device__ __forceinline__ void mg_lump_xr_row(double* __restrict__ acc, int lane, double c, const double4 T, int nt,
+                                               int has_z) {
+    const int t = (int)T.w;
+    if (has_z) acc[lane] += c * (T.x * T.x);
+    if (nt) {
+        const bool two = t + 1 < nt;
+        if (has_z) {
+            acc[(1 + t) * 64 + lane] += c * (T.x * T.y);
+            if (two) acc[(2 + t) * 64 + lane] += c * (T.x * T.z);
+        }
+        acc[(1 + nt + t) * 64 + lane] += c * (T.y * T.y);
+        if (two) {
+            acc[(2 + nt + t) * 64 + lane] += c * (T.z * T.z);
+            acc[(1 + 2 * nt + t) * 64 + lane] += c * (T.y * T.z);
+        }
+    }
+}
+
+// one lane per touched node (the nodes over XR_LONG rows are left to k_mg_lump_xr_long); the 64
+// nodes of a workgroup are then added to B node by node, entry k by lane k
+__global__ __launch_bounds__(64) void k_mg_lump_xr(int64_t nln, const int32_t* __restrict__ ln,
+                                                   const int64_t* __restrict__ lp, const int32_t* __restrict__ lr,
+                                                   const double* __restrict__ lw, const double4* __restrict__ lt,
+                                                   const double* __restrict__ rs, int nt, int nbB, int has_z,
+                                                   double* __restrict__ B) {
+    __shared__ double LA[MG_NB_MAX * 64];
+    __shared__ int32_t LN[64];
+    const int lane = threadIdx.x;
+    const int64_t j = (int64_t)blockIdx.x * 64 + lane;
+    for (int k = 0; k < nbB; ++k) LA[k * 64 + lane] = 0.0;
+    int32_t node = -1;
+    if (j < nln) {
+        const int64_t a = lp[j], e = lp[j + 1];
+        if (e - a <= XR_LONG) {
+            node = ln[j];
+            for (int64_t k = a; k < e; ++k) {
+                const int32_t r = lr[k];
+                const double s = rs[r];
+                mg_lump_xr_row(LA, lane, (s * s) * lw[k], lt[r], nt, has_z);
+            }
+        }
+    }
+    LN[lane] = node;
+    __syncthreads();
+    if (lane < nbB)
+        for (int i = 0; i < 64; ++i) {
+            const int32_t m = LN[i];
+            if (m >= 0) B[(int64_t)m * nbB + lane] += LA[lane * 64 + i];
+        }
+}
+
+// a wave per long node: lane l adds entries l, l + 64, … in row order, then the fixed shuffle tree
+// per block entry
+__global__ __launch_bounds__(64) void k_mg_lump_xr_long(int64_t nlong, const int32_t* __restrict__ longn,
+                                                        const int32_t* __restrict__ ln, const int64_t* __restrict__ lp,
+                                                        const int32_t* __restrict__ lr, const double* __restrict__ lw,
+                                                        const double4* __restrict__ lt, const double* __restrict__ rs,
+                                                        int nt, int nbB, int has_z, double* __restrict__ B) {
+    __shared__ double LA[MG_NB_MAX * 64];
+    const int lane = threadIdx.x;
+    if ((int64_t)blockIdx.x >= nlong) return;
+    const int32_t j = longn[blockIdx.x];
+    for (int k = 0; k < nbB; ++k) LA[k * 64 + lane] = 0.0;
+    const int64_t e = lp[j + 1];
+    for (int64_t k = lp[j] + lane; k < e; k += 64) {
+        const int32_t r = lr[k];
+        const double s = rs[r];
+        mg_lump_xr_row(LA, lane, (s * s) * lw[k], lt[r], nt, has_z);
+    }
+    double mine = 0.0;
+    for (int k = 0; k < nbB; ++k) {
+        const double s = wave_sum(LA[k * 64 + lane]);
+        if (lane == k) mine = s;
+    }
+    if (lane < nbB) B[(int64_t)ln[j] * nbB + lane] += mine;
 }
 
 // B_{ℓ+1}[m] = Σ_n P_nm B_ℓ[n] (lumping of a lumped block field: exact restriction)
@@ -1789,6 +1877,77 @@ void mg_var_coarse(System& S) {
     HIP_CHECK(hipStreamSynchronize(S.stream));
 }
 
+// Lumping requested for the extra rows (lsq_set_extra_rows_lumping): classify the formed rows and
+// build the transpose over the touched level-1 nodes for this hierarchy's geometry (xr_lump.hpp).
+// Kept across rebuilds of the hierarchy with the same geometry.  A refusal leaves lump_ok false
+// with its reason; xr_refusal reports it.
+void xr_lump_prepare(System& S) {
+    XrData& X = S.xr;
+    if (!X.m_x || !X.lump_req || !S.mg || S.mg->mixed || S.mg->dist) return;
+    const MgHier& H = *S.mg;
+    const MgGeom &g0 = H.lev[0].geo, &g1 = H.lev[1].geo;
+    XrLumpGeom G;
+    G.S0 = g0.S0, G.S1 = g0.S1, G.nt = g0.nt, G.has_z = g0.has_z;
+    G.colz = g0.colz, G.cold = g0.cold;
+    G.S0c = g1.S0, G.S1c = g1.S1;
+    if (X.lump_built && X.lump_geo == G) return;
+    X.lump_built = true;
+    X.lump_ok = false;
+    X.lump_geo = G;
+    const XrLumpHost L = xr_lump_build(G, X.m_x, X.st_rp.data(), X.st_ci.data(), X.st_val.data(), XR_LONG);
+    if (!L.ok) {
+        X.lump_why = L.why;
+        return;
+    }
+    hipStream_t st = S.stream;
+    auto up = [&](auto& buf, const auto& v) {
+        buf.alloc(std::max<int64_t>((int64_t)v.size(), 1));
+        if (!v.empty()) buf.upload(v.data(), (int64_t)v.size(), st);
+    };
+    up(X.l_tau, L.tau);
+    up(X.l_node, L.node);
+    up(X.l_ptr, L.ptr);
+    up(X.l_row, L.row);
+    up(X.l_w, L.w);
+    up(X.l_longn, L.long_node);
+    HIP_CHECK(hipStreamSynchronize(st));
+    X.l_rows = L.nrows;
+    X.l_nodes = (int64_t)L.node.size();
+    X.l_ent = L.ptr.back();
+    X.l_long = (int64_t)L.long_node.size();
+    X.l_dev_bytes = (int64_t)(X.l_tau.bytes() + X.l_node.bytes() + X.l_ptr.bytes() + X.l_row.bytes() + X.l_w.bytes() +
+                              X.l_longn.bytes());
+    X.lump_why.clear();
+    X.lump_ok = true;
+}
+
+// the extra rows ride this hierarchy: lumped on the coarse levels, exact on level 0
+inline bool xr_lumped(const System& S) { return xr_active(S) && S.xr.lump_req && S.xr.lump_ok; }
+
+// B_1 += the extra rows' lumped blocks for the current row scales (after mg_setup_lump1)
+void mg_setup_lump_xr(System& S) {
+    if (!xr_lumped(S)) return;
+    const XrData& X = S.xr;
+    const MgHier& H = *S.mg;
+    const double4* T = reinterpret_cast<const double4*>(X.l_tau.p);
+    const double* rs = S.rs.p + X.row0;
+    const int has_z = H.lev[0].geo.has_z;
+    if (X.l_nodes)
+        hipLaunchKernelGGL(k_mg_lump_xr, dim3((unsigned)((X.l_nodes + 63) / 64)), dim3(64), 0, S.stream, X.l_nodes,
+                           X.l_node.p, X.l_ptr.p, X.l_row.p, X.l_w.p, T, rs, H.nt, H.nbB, has_z, H.lev[1].B.p);
+    if (X.l_long)
+        hipLaunchKernelGGL(k_mg_lump_xr_long, dim3((unsigned)X.l_long), dim3(64), 0, S.stream, X.l_long, X.l_longn.p,
+                           X.l_node.p, X.l_ptr.p, X.l_row.p, X.l_w.p, T, rs, H.nt, H.nbB, has_z, H.lev[1].B.p);
+    KERNEL_CHECK();
+}
+
+// algorithmic bytes of one lumping pass: per entry its row id and w¹ (12 B) with the row's rs and τ
+// gathers (40 B); per touched node its id, pointer and block read and written
+double xr_lump_bytes(const System& S) {
+    const XrData& X = S.xr;
+    return 52.0 * (double)X.l_ent + (12.0 + 16.0 * (double)S.mg->nbB) * (double)X.l_nodes;
+}
+
 // A rank of a distributed solve (lsqr_cg_dist.inc group_mg_build): the global level-0 class tables
 // (from the global stencil description, lsq_dist_set_global), the global level-0 geometry, and the
 // rank's window rows (global node rows: window start wa, owned [oa, ob)).
@@ -2202,6 +2361,7 @@ bool mg_build(System& S, std::string& why, const MgDistInfo* di) {
     H->part1.alloc(2 * NPART);
     H->part2.alloc(2 * NPART);
     H->part_t.alloc(NPART);
+    H->part_x.alloc(XR_NPART);
     H->d0.alloc(S.n_full);
     H->d0.zero(S.stream);
     H->res0.alloc(S.n_full);
@@ -2213,6 +2373,7 @@ bool mg_build(System& S, std::string& why, const MgDistInfo* di) {
     HIP_CHECK(hipStreamSynchronize(S.stream));
     S.mg = guard.release();
     if (!di) mg_var_coarse(S);
+    if (!di) xr_lump_prepare(S);
     return true;
 }
 
@@ -2709,6 +2870,15 @@ void mg_launch_var(System& S, MgHier& H, int l, const CgState* st, const double*
                        betap, q);
 }
 
+// level 0 with lumped extra rows (xr_lumped): q += XᵀW_x²X p, exact as in the CG step, between the
+// data rows' Ad·p and the node gather.  k_xr_fwd's partials go to the hierarchy's own scratch
+// (nothing reads them here).
+void mg_launch_xr(System& S, MgHier& H, const CgState* st, const double* p, double* q) {
+    if (!xr_lumped(S)) return;
+    xr_launch_fwd(S, st, nullptr, p, 1.0, H.part_x.p);
+    xr_launch_atq(S, st, q);
+}
+
 // q = N_s x (+ the exact data rows on level 0) with p = z + β p_old formed by the ring kernel
 // (β from betap; p_old may be null; p written to pnew when non-null).  The operand the x-edge
 // correction and the data rows read is pnew, or z.
@@ -2782,6 +2952,7 @@ void mg_launch_op(System& S, MgHier& H, int l, const CgState* st, const double* 
         const double4* P = reinterpret_cast<const double4*>(S.dmf_pt.p);
         hipLaunchKernelGGL(k_cg_ad_xedge<8>, dim3(g.gD + ch.pad[0]), dim3(BLOCK), 0, S.stream, st, S.dmf, P, p, S.cg_t.p,
                            H.part_t.p, g.gD, cd, coef, q, V.part.p + V.gN);
+        mg_launch_xr(S, H, st, p, q);
         cg_launch_dmf_atq(S, st, S.cg_t.p, q);
     } else {   // field-valued parts: the x-edge correction and their rows beside t = Ad·p (side stream)
         HIP_CHECK(hipEventRecord(S.ev_fork, S.stream));
@@ -2793,6 +2964,7 @@ void mg_launch_op(System& S, MgHier& H, int l, const CgState* st, const double* 
         const double4* P = reinterpret_cast<const double4*>(S.dmf_pt.p);
         hipLaunchKernelGGL(k_cg_dmf_ad, dim3(g.gD), dim3(BLOCK), 0, S.stream, st, S.dmf, P, p, S.cg_t.p, H.part_t.p);
         HIP_CHECK(hipStreamWaitEvent(S.stream, S.ev_join, 0));
+        mg_launch_xr(S, H, st, p, q);   // after the join: the x-edge pass on S.side also updates q
         cg_launch_dmf_atq(S, st, S.cg_t.p, q);
     }
 }
@@ -3086,6 +3258,7 @@ void mg_setup(System& S) {
         return;
     }
     mg_setup_lump1(S);
+    mg_setup_lump_xr(S);
     mg_setup_rest(S, 0);
 }
 

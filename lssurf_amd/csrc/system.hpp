@@ -22,6 +22,7 @@
 
 #include "../../include/lsqsurf.h"
 #include "common.hpp"
+#include "xr_lump.hpp"
 
 namespace lsq {
 
@@ -345,6 +346,7 @@ constexpr int XR_LONG = 64;                 // rows above which a column is summ
 struct XrData {
     // staging (lsq_set_extra_rows before the formation)
     int64_t st_m = 0;
+    bool st_lump = false;           // lsq_set_extra_rows_lumping: asked for with the staged rows
     std::vector<int64_t> st_rp, st_ci;
     std::vector<double> st_val;
     // formed
@@ -364,6 +366,20 @@ struct XrData {
     DBuf<int32_t> tblk;             // touched column -> its column block (block.hip, per factorisation)
     DBuf<double> t;                 // m_x: rs · X p of the current step
     int64_t dev_bytes = 0;
+    // the multigrid's lumped rows (xr_lump.hpp; mg.inc: xr_lump_prepare, k_mg_lump_xr), built with
+    // the hierarchy when lumping was requested
+    bool lump_req = false;          // requested for the formed rows
+    bool lump_built = false, lump_ok = false;
+    std::string lump_why;
+    XrLumpGeom lump_geo;
+    int64_t l_rows = 0, l_nodes = 0, l_ent = 0, l_long = 0;
+    DBuf<double> l_tau;             // 4 per row: τ_z, τ_t, τ_{t+1}, t
+    DBuf<int32_t> l_node;           // touched level-1 nodes, ascending
+    DBuf<int64_t> l_ptr;
+    DBuf<int32_t> l_row;            // local row of each entry (ascending within a node)
+    DBuf<double> l_w;               // its w¹
+    DBuf<int32_t> l_longn;          // positions in l_node of the nodes over XR_LONG rows
+    int64_t l_dev_bytes = 0;
 };
 
 struct System {

@@ -11,6 +11,9 @@
 // Both run between the data rows' Ad·p and the node gather q += Adᵀ td, whose fused α then sees the
 // new partials.  Every sum has a fixed order and no atomics: two runs agree bit for bit.  Launch
 // counts and grids depend on m_x and the touched columns only.
+// With lsq_set_extra_rows_lumping the multigrid (precond 4) carries the rows too: level 0 of the
+// V-cycle launches the same two kernels (mg.inc, mg_launch_xr) and the coarse levels take the rows
+// lumped into their node blocks (xr_lump.hpp, k_mg_lump_xr).
 
 // t[r] = rs[r] · ((b ? b[r] : 0) + sgn · Σ v · p[col]) per extra row and part[blockIdx.x] = Σ t².
 // The CG step: b = null, sgn = 1; the initial residual: b, p = x0 (or null), sgn = −1.

@@ -18,6 +18,7 @@ are outside lssurf_amd's scope and raise NotImplementedError instead of silently
 The dz priors (prior_args, prior_edge_args; match_priors.py) take in-memory grids; their rows stay
 last in Gc and the device carries them as extra rows inside matrix-free CGNR (lsq_set_extra_rows).
 With priors compute_E, n_gpus > 1 and lsq_bias='eliminate' raise NotImplementedError.
+lsq_prior_mg=True lets the multigrid preconditioner (precond 4) carry them, lumped into its coarse levels.
 Data biases (bias_params) run when the solver key lsq_bias says how: 'eliminate' (the device
 eliminates them inside CGNR, lsq_set_data_bias), 'columns' (ordinary columns of a generic system)
 or 'auto' (with priors: 'columns', with a warning where it would have eliminated).
@@ -60,7 +61,10 @@ DEFAULTS = {'reference_epoch': 0, 'W_ctr': 1e4, 'return_fit_objects': False, 'ma
             'lsq_precond': 'auto', 'lsq_dense_max': 16384, 'lsq_warm_start': True, 'lsq_method': 'auto',
             'lsq_reuse_anorm': True, 'lsq_E_method': 'auto', 'n_gpus': 1, 'devices': None,
             # data biases (bias_params): None refuses them; 'eliminate', 'columns' or 'auto'
-            'lsq_bias': None}
+            'lsq_bias': None,
+            # priors (prior_args / prior_edge_args) inside the multigrid preconditioner: their rows
+            # lumped into its coarse levels (opt-in; without priors the key does nothing)
+            'lsq_prior_mg': False}
 
 OUT_OF_SCOPE = ('sensor_grid_bias_params', 'lagrangian_coords',
                 'constraint_scaling_maps', 'mask_file', 'bias_edit_vals')
@@ -71,7 +75,7 @@ class FitSystem:
     Ip_c as a column map; rows re-weighted / re-selected per outer iteration."""
 
     def __init__(self, G_data, Gc, keep_cols, n_full, device=0, structured=True, grids=None, bias=None,
-                 extra_ops=None, extra_csr=None):
+                 extra_ops=None, extra_csr=None, extra_mg=False):
         """bias = (ids, c): eliminated data biases (LSQSolver.set_data_bias) — G_data and Gc are then
         the grid-only operators, the caller's row weights and rhs may carry further (bias
         constraint) rows behind them, and the biases take the columns after n_full in expand().
@@ -81,7 +85,11 @@ class FitSystem:
         carries them; if the device refuses, the whole system takes the COO path.
         extra_csr = (indptr, cols_full, vals): extra rows that are not in Gc at all, behind its last
         row (the row weights, mask and rhs of solve() then have n_data + Gc.N_eq + their count
-        entries); they need the structured formation."""
+        entries); they need the structured formation.
+        extra_mg: ask the device to lump the extra rows into the multigrid's coarse levels
+        (LSQSolver.set_extra_rows(lump=True)), so that precond 4 may carry them; where the device
+        refuses (e.g. a row over non-adjacent epochs) multigrid_available warns with its reason and
+        the system stays on block-Jacobi."""
         self.n_data, self.n_con = int(G_data.N_eq), int(Gc.N_eq)
         self.keep_cols = keep_cols
         self.n_full = int(n_full)
@@ -109,7 +117,8 @@ class FitSystem:
             # matrix-free ('extra rows need …').  Any other formation error stays an error.
             try:
                 if n_extra:        # staged first: they become the last rows of the formation
-                    self.solver.set_extra_rows(*(extra_csr if extra_csr is not None else _extra_rows_csr(extra_ops)))
+                    self.solver.set_extra_rows(*(extra_csr if extra_csr is not None else _extra_rows_csr(extra_ops)),
+                                               lump=bool(extra_mg))
                 refusal = None
             except NativeError as e:
                 if extra_csr is not None:
@@ -155,9 +164,11 @@ class FitSystem:
                     self.solver.set_column_blocks_csr(*blocks)
                     self.has_blocks = True
                     self._blocks = blocks
-        # multigrid (precond 4) availability, probed on first use; never with extra rows: the coarse
-        # levels would not carry their term, so 'auto' takes block-Jacobi as with eliminated biases
-        self._mg = False if self.n_extra else None
+        # multigrid (precond 4) availability, probed on first use; with extra rows only when their
+        # lumping was requested (extra_mg): otherwise the coarse levels would not carry their term, so
+        # 'auto' takes block-Jacobi as with eliminated biases
+        self.extra_mg = bool(extra_mg) and self.n_extra > 0
+        self._mg = False if (self.n_extra and not self.extra_mg) else None
         self.mg_build_s = 0.0
         self.stats = None
         self.bias_ids, self.bias_vals = None, None
@@ -195,8 +206,12 @@ class FitSystem:
                     self.solver.set_row_weight(row_weight)
                     self._w_last = row_weight
                 tic = time()
-                self._mg = bool(self.solver.cg_available(4)[0])   # builds the level hierarchy
+                ok, why = self.solver.cg_available(4)   # builds the level hierarchy
+                self._mg = bool(ok)
                 self.mg_build_s = time() - tic
+                if not ok and self.extra_mg:
+                    warnings.warn(f'FitSystem: multigrid does not carry the {self.n_extra} extra rows ({why}); '
+                                  f'the system stays on block-Jacobi', RuntimeWarning, stacklevel=2)
         return self._mg
 
     def solve(self, row_weight, data_keep, rhs, x0=None, **opts):
@@ -382,6 +397,8 @@ def iterate_fit(data, system, rhs, TCinv, G_data, Gc, in_TSE, timing, args, grid
             print(f"smooth_fit: LSQR reached its iteration limit ({system.stats['iters']}) before the "
                   f"requested tolerance; raise lsq_maxit or use lsq_precond=2", flush=True)
         system.stats['precond'] = opts['precond']
+        # did this solve run the multigrid with the priors' rows lumped into it (lsq_prior_mg)?
+        timing['prior_mg'] = bool(opts['precond'] == 4 and getattr(system, 'n_extra', 0) > 0)
         prev_solve = (weight, np.asarray(in_TSE, bool).copy() if opts['precond'] == 4 else None)
         system.last_x = x   # compact solution: z_est and the constraint statistics read it, not m0
         timing['sparseqr_solve'] = time() - tic
@@ -650,6 +667,8 @@ def smooth_fit(**kwargs):
             raise NotImplementedError(f'smooth_fit: {key!r} is outside lssurf_amd (SURVEY.md §2)')
     if args.get('data_slope_sensors') is not None and len(args['data_slope_sensors']) > 0:
         raise NotImplementedError("smooth_fit: 'data_slope_sensors' is outside lssurf_amd")
+    if not isinstance(args['lsq_prior_mg'], (bool, np.bool_)):
+        raise ValueError(f"smooth_fit: lsq_prior_mg must be True or False, not {args['lsq_prior_mg']!r}")
     bias_mode = args['lsq_bias']
     if args['bias_params'] is not None:
         if bias_mode is None:
@@ -810,7 +829,7 @@ def smooth_fit(**kwargs):
                                           bias_mode, grids, devices[0], args, prior_ops=prior_ops)
             else:
                 system = FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=devices[0], grids=grids,
-                                   extra_ops=prior_ops)
+                                   extra_ops=prior_ops, extra_mg=bool(args['lsq_prior_mg']) and bool(prior_ops))
             if b_rows_all is not None and not getattr(system, 'n_extra', 0):
                 b_rows = max(b_rows, b_rows_all)
             system.b_rows = b_rows

@@ -93,10 +93,12 @@ class LSQSolver:
             self.n = int(n_full)
         self.n_full = int(n_full)
 
-    def set_extra_rows(self, indptr, cols_full, vals):
+    def set_extra_rows(self, indptr, cols_full, vals, lump=False):
         """Extra sparse rows behind the stencil rows (lsq_set_extra_rows), staged before
         set_matrix_stencil: a CSR over the full column space, at most 32 entries per row after
-        duplicates are summed and zeros and removed columns dropped.  indptr = None clears."""
+        duplicates are summed and zeros and removed columns dropped.  indptr = None clears.
+        lump: ask the multigrid (precond 4) to carry the rows, lumped into its coarse levels' node
+        blocks (lsq_set_extra_rows_lumping); cg_available(4) tells whether it can."""
         if indptr is None or np.size(indptr) <= 1:
             self._check(self._L.lsq_set_extra_rows(self._h, 0, None, None, None), 'lsq_set_extra_rows')
             return
@@ -104,12 +106,27 @@ class LSQSolver:
         vals = as_c(vals, np.float64)
         self._check(self._L.lsq_set_extra_rows(self._h, indptr.size - 1, ptr(indptr), ptr(cols_full), ptr(vals)),
                     'lsq_set_extra_rows')
+        self._check(self._L.lsq_set_extra_rows_lumping(self._h, 1 if lump else 0), 'lsq_set_extra_rows_lumping')
+
+    def extra_rows_mg_info(self):
+        """{rows lumped, touched level-1 nodes, bytes of one lumping pass, device bytes of its tables}
+        of the extra rows inside the multigrid (zeros when precond 4 does not carry them)."""
+        o = np.zeros(4)
+        self._check(self._L.lsq_extra_rows_mg_info(self._h, ptr(o)), 'lsq_extra_rows_mg_info')
+        return {'rows': int(o[0]), 'nodes': int(o[1]), 'pass_bytes': float(o[2]), 'device_bytes': int(o[3])}
 
     def extra_rows_info(self):
         """{rows, touched columns, step bytes (xr_step_bytes), device bytes} of the extra rows."""
         o = np.zeros(4)
         self._check(self._L.lsq_extra_rows_info(self._h, ptr(o)), 'lsq_extra_rows_info')
         return {'m_x': int(o[0]), 'touched_cols': int(o[1]), 'step_bytes': float(o[2]), 'device_bytes': int(o[3])}
+
+    def profile_extra_rows_lumping(self, reps=20):
+        """Device time (ms) of the extra rows' lumping pass in the multigrid set-up (k_mg_lump_xr and its
+        long-node kernel) and of the data rows' k_mg_lump1 before it."""
+        o = np.zeros(2)
+        self._check(self._L.lsq_profile_extra_rows_lumping(self._h, int(reps), ptr(o)), 'lsq_profile_extra_rows_lumping')
+        return {'k_mg_lump_xr': float(o[0]), 'k_mg_lump1': float(o[1])}
 
     def profile_extra_rows(self, reps=20, precond=3):
         """Device time (ms) of the extra rows' kernels inside real iterations (after iterate() with the

@@ -17,8 +17,15 @@ and one with these extra rows:
    them and the node gather behind them for scale.
 2. a converged block-Jacobi solve (atol = btol = 1e-12) on each: the iteration counts.
 3. the device bytes of the extra rows and their transpose.
+4. (--mg OUT_MG.json) the multigrid leg: the prior handle is formed with the rows' lumping requested
+   (FitSystem(extra_mg=True); the block-Jacobi numbers above do not depend on it).  Converged solves
+   (atol = btol = 1e-12) of block-Jacobi with priors, multigrid with lumped priors and multigrid
+   without priors: iterations, time_s, setup_s.  The device time of one lumping pass of the set-up
+   (k_mg_lump_xr with its long-node kernel, lsq_profile_extra_rows_lumping) against its byte model,
+   and the added time per multigrid iteration (alternating lsq_iterate rounds of the two handles
+   with precond 4; a V-cycle applies level 0 five times) against 5 × this run's k_xr_fwd + k_xr_atq.
 
-Usage: python tools/prior_step.py OUT.json [--config c4] [--steps 200] [--rounds 5] [--no-solves]
+Usage: python tools/prior_step.py OUT.json [--config c4] [--steps 200] [--rounds 5] [--no-solves] [--mg OUT_MG.json]
 """
 import argparse
 import json
@@ -51,6 +58,57 @@ def frame_rows(gd, ref, tile_nodes, strip_nodes):
     return np.arange(0, 2 * n + 1, 2, dtype=np.int64), cols, vals
 
 
+def multigrid_leg(a, res, cases):
+    """the priors inside the multigrid preconditioner (lumped into its coarse levels) at this size"""
+    sys_plain, sys_prior = cases['plain'][0], cases['prior'][0]
+    out = {k: res[k] for k in ('config', 'n_points', 'n_cols', 'tile_nodes', 'sigma', 'budget_rate_bytes_per_s')}
+    out['extra_rows'] = res['extra_rows']
+    ok, why = sys_prior.solver.cg_available(4)
+    if not ok:
+        raise RuntimeError(f'the multigrid does not carry the priors: {why}')
+    out['levels'] = [list(map(int, lv)) for lv in sys_prior.solver.mg_info()[0]]
+    out['lumping'] = sys_prior.solver.extra_rows_mg_info()
+    lump = sys_prior.solver.profile_extra_rows_lumping(reps=20)
+    out['lump_pass_us'] = 1e3 * lump['k_mg_lump_xr']
+    out['lump1_us'] = 1e3 * lump['k_mg_lump1']
+    out['lump_pass_budget_us'] = 1e6 * out['lumping']['pass_bytes'] / res['budget_rate_bytes_per_s']
+    out['lump_pass_bytes_per_s'] = out['lumping']['pass_bytes'] / max(1e-3 * lump['k_mg_lump_xr'], 1e-12)
+    # converged solves, cold starts
+    out['solves'] = {}
+    xs = {}
+    for label, name, pc in (('block_jacobi_priors', 'prior', 3), ('multigrid_lumped_priors', 'prior', 4),
+                            ('multigrid_no_priors', 'plain', 4)):
+        fs, _, b = cases[name]
+        runs = []
+        for _ in range(3):
+            xs[label], st = fs.solver.solve(b, precond=pc, method=1, maxit=200000, b_rows=fs.n_data, **TOL)
+            runs.append({'iters': int(st['iters']), 'istop': int(st['istop']), 'time_s': float(st['time_s']),
+                         'setup_s': float(st.get('setup_s', 0.))})
+        best = min(runs, key=lambda r: r['time_s'])
+        out['solves'][label] = dict(best, runs=runs)
+        print(label, out['solves'][label], flush=True)
+    xb, xm = xs['block_jacobi_priors'], xs['multigrid_lumped_priors']
+    out['solution_rel_diff'] = float(np.linalg.norm(xm - xb) / np.linalg.norm(xb))
+    # the step: alternating rounds of precond 4 iterations on the two handles
+    t = {'plain': [], 'prior': []}
+    for _ in range(a.rounds):
+        for name in t:
+            fs, _, b = cases[name]
+            fs.solver.iterate(b, 8, precond=4, method=1, b_rows=fs.n_data)
+            st = fs.solver.iterate(b, a.mg_steps, precond=4, method=1, b_rows=fs.n_data)
+            t[name].append(1e3 * st['time_s'] / a.mg_steps)
+    e = {'steps': a.mg_steps, 'step_ms_plain': float(np.median(t['plain'])), 'step_ms_prior': float(np.median(t['prior'])),
+         'step_ms_plain_all': t['plain'], 'step_ms_prior_all': t['prior']}
+    e['extra_us'] = 1e3 * (e['step_ms_prior'] - e['step_ms_plain'])
+    if 'step' in res:   # level 0 is applied five times per iteration: the CG step, one pre-smoothing step, the
+        k = res['step']['kernels_us']   # residual, two post-smoothing steps
+        e['kernels_us'] = {n: k[n] for n in ('k_xr_fwd', 'k_xr_atq')}
+        e['five_applications_us'] = 5. * (k['k_xr_fwd'] + k['k_xr_atq'])
+    out['step'] = e
+    print(e, flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('out')
@@ -60,6 +118,8 @@ def main():
     ap.add_argument('--tile-km', type=float, default=80.)
     ap.add_argument('--strip-km', type=float, default=3.)
     ap.add_argument('--no-solves', action='store_true')
+    ap.add_argument('--mg', default=None, help='write the multigrid leg (lumped priors) to this file')
+    ap.add_argument('--mg-steps', type=int, default=48)
     a = ap.parse_args()
 
     import lssurf_amd as LS
@@ -81,7 +141,8 @@ def main():
     wx = np.full(m_x, 1. / 0.1)
     prior = 0.05 * np.random.default_rng(1).standard_normal(m_x)
     sys_plain = FitSystem(S['G_data'], S['Gc'], keep, S['Gc'].col_N, grids=S['grids'])
-    sys_prior = FitSystem(S['G_data'], S['Gc'], keep, S['Gc'].col_N, grids=S['grids'], extra_csr=csr)
+    sys_prior = FitSystem(S['G_data'], S['Gc'], keep, S['Gc'].col_N, grids=S['grids'], extra_csr=csr,
+                          extra_mg=a.mg is not None)
     cases = {'plain': (sys_plain, w, rhs), 'prior': (sys_prior, np.r_[w, wx], np.r_[rhs, prior])}
     res = {'config': a.config, 'n_points': int(sys_plain.n_data), 'n_cols': int(keep.size), 'steps': a.steps,
            'rounds': a.rounds, 'tile_nodes': tile_nodes, 'sigma': 0.1, 'timing': 'device events around the '
@@ -137,6 +198,8 @@ def main():
                 res['solve_block_jacobi'][name] = {'iters': int(st['iters']), 'istop': int(st['istop']),
                                                    'time_s': float(st['time_s'])}
                 print(name, res['solve_block_jacobi'][name], flush=True)
+        if a.mg:
+            res_mg = multigrid_leg(a, res, cases)
     finally:
         sys_plain.close()
         sys_prior.close()
@@ -144,6 +207,11 @@ def main():
     with open(a.out, 'w') as f:
         json.dump(res, f, indent=1)
     print(json.dumps(res))
+    if a.mg:
+        os.makedirs(os.path.dirname(os.path.abspath(a.mg)), exist_ok=True)
+        with open(a.mg, 'w') as f:
+            json.dump(res_mg, f, indent=1)
+        print(json.dumps(res_mg))
 
 
 if __name__ == '__main__':
