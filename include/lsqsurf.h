@@ -492,7 +492,8 @@ int lsq_normal_apply(lsq_handle* h, const double* p, double* q);
  * W = the data rows' current weight × mask), so x keeps its length.
  * lsq_set_data_bias: call after lsq_set_matrix_stencil.  id[i] ∈ [0, nb) for data row i in the
  * caller's row order, c[j] > 0; npts must equal the system's data rows.  nb = 0 or a null pointer
- * clears the biases.  Returns −2 (the handle and any biases set before stay as they were) on an ID
+ * clears the biases; setting or clearing them also clears the slopes of lsq_set_data_slope (below),
+ * which index the bias IDs.  Returns −2 (the handle and any biases set before stay as they were) on an ID
  * out of range, a c that is not > 0, or a wrong npts.  The biases belong to the handle's matrix: a
  * handle takes one matrix (a second lsq_set_matrix_* returns −2 and changes nothing, the biases
  * included), and every formation of the operator starts without biases.
@@ -504,6 +505,32 @@ int lsq_normal_apply(lsq_handle* h, const double* p, double* q);
  * b_j = Σ_{i∈j} W_i² (d_i − (A_d x)_i) / D_j (0 for an ID no row carries); −2 before any solve. */
 int lsq_set_data_bias(lsq_handle* h, int64_t npts, const int32_t* id, int64_t nb, const double* c);
 int lsq_get_data_bias(lsq_handle* h, double* b);
+
+/* Slope biases: the data rows of slope group s gain two further unknowns γ_s (a tilt in x and in y,
+ * smooth_fit's data_slope_sensors) with the coefficients u[2i], u[2i + 1] on row i and the constraint
+ * rows c[2s] γ_s0 = 0, c[2s + 1] γ_s1 = 0.  They are eliminated together with the data biases: with
+ * Z = [B U] (B the bias indicator columns, U the slope columns) and M = ZᵀW²Z + C², the normal operator
+ * is AᵀA − A_dᵀ W² Z M⁻¹ Zᵀ W² A_d.  The layout must be nested: the rows of every bias ID lie in at most
+ * one slope group (rows of group −1 do not count; always true when the sensor is among the bias
+ * parameters and the groups are sensors).  M⁻¹ is then one 2 × 2 system per group.
+ * lsq_set_data_slope: call after lsq_set_matrix_stencil and, if biases are used, after
+ * lsq_set_data_bias.  grp[i] ∈ {−1} ∪ [0, ng) for data row i in the caller's row order; u is read only
+ * where grp ≥ 0; c > 0.  ng = 0 or a null pointer clears the slopes (the biases stay, and solve as if
+ * no slopes had ever been set, bit for bit).  lsq_set_data_bias, when it sets or clears the biases,
+ * clears the slopes too.  Returns −2 with the handle unchanged on a group out of range, a u that is
+ * not finite, a c that is not > 0, a wrong npts or a layout that is not nested.
+ * Solves, lsq_cg_available and lsq_normal_apply follow the rules of the data biases above, with or
+ * without biases set.  Every sum runs in a fixed order without atomics: results are bitwise equal
+ * run to run.
+ * lsq_get_data_slope: the 2·ng slopes that belong to the last lsq_solve's x (0 for a group no row
+ * carries); −2 before any solve. */
+int lsq_set_data_slope(lsq_handle* h, int64_t npts, const int32_t* grp, const double* u, int64_t ng, const double* c);
+int lsq_get_data_slope(lsq_handle* h, double* g);
+/* The slope elimination's kernels timed inside reps real iterations of the live lsq_iterate state
+ * (method 1, this precond; HIP events between the launches): out8 = {ms of the chunk pass, of the
+ * per-rank sums, of the per-group kernel, of the apply pass, and the algorithmic HBM bytes of each}.
+ * −2 without such a state or without slopes in the operator. */
+int lsq_profile_data_slope(lsq_handle* h, int32_t reps, int32_t precond, double* out8);
 int lsq_sell_info(lsq_handle* h, int64_t* out8);
 
 /* ---- triangular kernels (replace the Cython kernels; R upper triangular CSR, int32 indices,

@@ -21,6 +21,10 @@ void bias_set(System& S, int64_t npts, const int32_t* h_id, int64_t nb, const do
 void bias_clear(System& S);
 void bias_get(System& S, double* h_b);
 std::string bias_refusal(System& S, int method, int precond);
+void slope_set(System& S, int64_t npts, const int32_t* h_grp, const double* h_u, int64_t ng, const double* h_c);
+void slope_clear(System& S);
+void slope_get(System& S, double* h_g);
+void cg_profile_slope(System& S, int reps, int precond, double* out8);
 std::string xr_refusal(System& S, int method, int precond, int op);
 void xr_info(System& S, double* out4);
 void xr_mg_info(System& S, double* out4);
@@ -407,7 +411,7 @@ int lsq_solve(lsq_handle* h, const double* b, double* x_inout, const lsq_opts* o
         if (o->method != 0 && o->method != 1) return fail(S, "lsq_solve: method must be 0 (LSQR) or 1 (CGNR)");
         if (o->precond < 0 || o->precond > 5) return fail(S, "lsq_solve: precond must be 0 .. 5");
         if (o->precond == 5 && S.dist) return fail(S, "lsq_solve: precond 5 (band factor) is single-GPU");
-        if (S.bias.nb) {
+        if (S.bias.nb || S.bias.ng) {
             const std::string why = lsq::bias_refusal(S, o->method, o->precond);
             if (!why.empty()) return fail(S, "lsq_solve: " + why);
         }
@@ -448,7 +452,7 @@ int lsq_iterate(lsq_handle* h, const double* b, int64_t iters, const lsq_opts* o
         lsq_opts d;
         lsq_default_opts(&d);
         if (!o) o = &d;
-        if (S.bias.nb) {
+        if (S.bias.nb || S.bias.ng) {
             const std::string why = lsq::bias_refusal(S, o->method, o->precond);
             if (!why.empty()) return fail(S, "lsq_iterate: " + why);
         }
@@ -478,7 +482,7 @@ int lsq_cg_available(lsq_handle* h, int32_t precond) {
             S.err = "CGNR runs with precond 1 (Jacobi), 3 (block-Jacobi) or 4 (multigrid)";
             return 0;
         }
-        if (S.bias.nb) {   // biases set: only the matrix-free CGNR operator carries them
+        if (S.bias.nb || S.bias.ng) {   // biases or slopes set: only the matrix-free CGNR operator carries them
             const std::string why = lsq::bias_refusal(S, 1, precond);
             if (!why.empty()) {
                 S.err = why;
@@ -576,6 +580,37 @@ int lsq_get_data_bias(lsq_handle* h, double* b) {
     return guarded(h, [&](lsq::System& S) {
         if (!b) return fail(S, "lsq_get_data_bias: null output");
         lsq::bias_get(S, b);
+        return 0;
+    });
+}
+
+int lsq_set_data_slope(lsq_handle* h, int64_t npts, const int32_t* grp, const double* u, int64_t ng, const double* c) {
+    return guarded(h, [&](lsq::System& S) {
+        if (!S.G.rp.p) return fail(S, "lsq_set_data_slope: no matrix");
+        if (ng < 0 || npts < 0) return fail(S, "lsq_set_data_slope: bad sizes");
+        if (ng == 0 || !grp || !u || !c) {
+            lsq::slope_clear(S);
+            return 0;
+        }
+        lsq::slope_set(S, npts, grp, u, ng, c);
+        return 0;
+    });
+}
+
+int lsq_get_data_slope(lsq_handle* h, double* g) {
+    return guarded(h, [&](lsq::System& S) {
+        if (!g) return fail(S, "lsq_get_data_slope: null output");
+        lsq::slope_get(S, g);
+        return 0;
+    });
+}
+
+int lsq_profile_data_slope(lsq_handle* h, int32_t reps, int32_t precond, double* out8) {
+    return guarded(h, [&](lsq::System& S) {
+        if (!S.G.rp.p) return fail(S, "lsq_profile_data_slope: no matrix");
+        if (!out8) return fail(S, "lsq_profile_data_slope: null output");
+        lsq::graph_cache_drop(&S);
+        lsq::cg_profile_slope(S, reps > 0 ? reps : 10, precond, out8);
         return 0;
     });
 }

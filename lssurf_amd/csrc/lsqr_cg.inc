@@ -2353,8 +2353,7 @@ void cg_init(System& S, const double* h_b, const double* h_x0, const lsq_opts& o
             hipLaunchKernelGGL(k_bias_resid, dim3(ge), dim3(BLOCK), 0, st, B.npts, S.dmf_perm.p, B.w2.p, dbp, S.cg_t.p,
                                S.cg_t.p);
             bias_launch_reduce(S, nullptr, S.cg_t.p, S.part_u.p + nu);
-            hipLaunchKernelGGL(k_bias_apply, dim3(ge), dim3(BLOCK), 0, st, nullptr, B.npts, B.rank_pt.p, B.w2.p, B.sD.p,
-                               S.cg_t.p, 1);
+            bias_launch_apply(S, nullptr, S.cg_t.p, 1);
             cg_launch_dmf_atq(S, S.cst.p, S.cg_t.p, S.cg_s.p);
             KERNEL_CHECK();
         }
@@ -2509,7 +2508,7 @@ int cg_solve(System& S, const double* h_b, double* h_x, const lsq_opts& o, lsq_s
     KERNEL_CHECK();
     dx.download(h_x, n, S.stream);
     HIP_CHECK(hipStreamSynchronize(S.stream));
-    if (S.bias.nb) bias_values(S, S.rhs.p);   // the biases that belong to this x
+    if (S.bias.nb || S.bias.ng) bias_values(S, S.rhs.p);   // the biases and slopes that belong to this x
     float ms = 0.f;
     HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
     (void)hipEventDestroy(e0);
@@ -2707,6 +2706,57 @@ void cg_profile_xr(System& S, int reps, int precond, double* out) {
     for (int k = 0; k < 4; ++k) out[k] = t[k] / reps;
 }
 
+// The slope elimination's kernels inside real iterations of a live lsq_iterate state (no stop), events
+// between the launches as in cg_profile_xr: out8 = {ms chunk pass, ms per-rank sums (with the long
+// ranks), ms per-group kernel, ms apply pass, and their algorithmic bytes (slope_kernel_bytes)}, means
+// over reps iterations.
+void cg_profile_slope(System& S, int reps, int precond, double* out) {
+    if (!(S.cg_ready && S.cg_mode == precond))
+        throw std::invalid_argument("lsq_profile_data_slope: needs the live state of lsq_iterate with this precond");
+    if (!bias_active(S) || !S.bias.ng) throw std::invalid_argument("lsq_profile_data_slope: no slopes in the CGNR operator");
+    const CgGrids g = cg_grids(S, precond);
+    std::vector<hipEvent_t> ev(5 * reps);
+    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+    for (int r = 0; r < reps; ++r) {
+        const int par = S.cg_parity;
+        const double* pold = cg_pold(S, par);
+        double* pnew = cg_pnew(S, par);
+        hipEvent_t* e = ev.data() + 5 * r;
+        double* part = S.cg_part_t.p + g.gD;
+        cg_launch_normal(S, g, pold, pnew);
+        hipLaunchKernelGGL(k_cg_dmf_ad, dim3(g.gD), dim3(BLOCK), 0, S.stream, S.cst.p, S.dmf,
+                           reinterpret_cast<const double4*>(S.dmf_pt.p), pnew, S.cg_t.p, S.cg_part_t.p);
+        HIP_CHECK(hipEventRecord(e[0], S.stream));
+        bias_launch_chunks(S, S.cst.p, S.cg_t.p);
+        HIP_CHECK(hipEventRecord(e[1], S.stream));
+        bias_launch_seg(S, S.cst.p, 1, part);
+        HIP_CHECK(hipEventRecord(e[2], S.stream));
+        slope_launch_group(S, S.cst.p, 2, part + S.bias.nrk);
+        HIP_CHECK(hipEventRecord(e[3], S.stream));
+        bias_launch_apply(S, S.cst.p, S.cg_t.p, 0);
+        HIP_CHECK(hipEventRecord(e[4], S.stream));
+        cg_launch_xr(S, g, pnew);
+        cg_launch_atdq(S);
+        cg_launch_alpha(S, g);
+        cg_launch_precond(S, g, precond);
+        hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(BLOCK), 0, S.stream, S.cst.p, S.cg_part_r.p, g.gB, 0, nullptr);
+        S.cg_parity = (S.cg_parity + 1) % CG_XK;
+    }
+    HIP_CHECK(hipStreamSynchronize(S.stream));
+    double t[4] = {0, 0, 0, 0};
+    for (int r = 0; r < reps; ++r) {
+        hipEvent_t* e = ev.data() + 5 * r;
+        for (int k = 0; k < 4; ++k) {
+            float a = 0.f;
+            HIP_CHECK(hipEventElapsedTime(&a, e[k], e[k + 1]));
+            t[k] += a;
+        }
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+    for (int k = 0; k < 4; ++k) out[k] = t[k] / reps;
+    slope_kernel_bytes(S, out + 4);
+}
+
 // The lumping pass of the multigrid set-up in place (lsq_profile_extra_rows_lumping): reps times the
 // level-1 blocks of the data rows (k_mg_lump1) and then the extra rows' share (k_mg_lump_xr and its
 // long-node kernel), events between them: out2 = {ms of the extra rows' pass, ms of k_mg_lump1}.
@@ -2790,7 +2840,7 @@ void cg_apply_normal(System& S, const double* h_p, double* h_q) {
     S.cg_ready = false;
 }
 
-// ---- data biases (bias.inc): set, clear, read back ---------------------------------------------
+// ---- data biases and slopes (bias.inc, slope.inc): set, clear, read back -------------------------
 void bias_clear(System& S) {
     if (!S.bias.on && !S.bias.idx.p) return;
     graph_cache_drop(&S);   // captured iterations hold the step's launches
@@ -2798,7 +2848,144 @@ void bias_clear(System& S) {
     S.cg_ready = false;
 }
 
-// id: the data rows' bias IDs in the caller's row order; c: 1 / E_bias per ID
+namespace {
+// The layout of the eliminated columns.  h_id: the data rows' bias IDs in the caller's row order
+// (null: no biases, the slopes' pseudo-IDs), h_c: 1 / E_bias per ID; h_grp (null: no slopes), h_u,
+// h_gc: the rows' slope groups, their coefficients and the groups' c.  Arguments are valid.
+void bias_build(System& S, int64_t npts, const int32_t* h_id, int64_t nb, const double* h_c, const int32_t* h_grp,
+                const double* h_u, int64_t ng, const double* h_gc) {
+    std::vector<int32_t> perm(std::max<int64_t>(npts, 1));
+    S.dmf_perm.download(perm.data(), npts, S.stream);
+    HIP_CHECK(hipStreamSynchronize(S.stream));
+    std::vector<int32_t> keep_id, keep_grp;   // the caller's arrays outlive the previous layout
+    std::vector<double> keep_c;
+    if (h_id) {
+        keep_id.assign(h_id, h_id + npts);
+        keep_c.assign(h_c, h_c + nb);
+    }
+    if (h_grp) keep_grp.assign(h_grp, h_grp + npts);
+    bias_clear(S);
+    graph_cache_drop(&S);   // captured iterations hold no elimination step yet
+    S.cg_ready = false;
+    const bool pseudo = !h_id;
+    const int64_t ne = pseudo ? ng + 1 : nb;   // IDs, or one pseudo-ID per group and one for the rows outside
+    auto eid = [&](int64_t i) -> int32_t { return pseudo ? (h_grp[i] < 0 ? (int32_t)ng : h_grp[i]) : h_id[i]; };
+    // ranks: the IDs that carry points, in ID order; slopes set: by (group, ID), the IDs outside every
+    // group last.  The sorted points are indexed stably by rank.
+    std::vector<int32_t> cnt(ne + 1, 0), rank_of(ne, -1), rank_id, sgrp(h_grp ? ne : 0, -1);
+    for (int64_t i = 0; i < npts; ++i) {
+        ++cnt[eid(i)];
+        if (h_grp && h_grp[i] >= 0) sgrp[eid(i)] = h_grp[i];
+    }
+    for (int64_t j = 0; j < ne; ++j)
+        if (cnt[j]) rank_id.push_back((int32_t)j);
+    int64_t nsr = 0;
+    std::vector<int32_t> gseg(ng + 1, 0), rgrp;
+    if (h_grp) {
+        std::stable_sort(rank_id.begin(), rank_id.end(), [&](int32_t x, int32_t y) {
+            return (sgrp[x] < 0 ? ng : sgrp[x]) < (sgrp[y] < 0 ? ng : sgrp[y]);
+        });
+        for (int32_t j : rank_id)
+            if (sgrp[j] >= 0) {
+                ++gseg[sgrp[j] + 1];
+                rgrp.push_back(sgrp[j]);
+                ++nsr;
+            }
+        for (int64_t g = 0; g < ng; ++g) gseg[g + 1] += gseg[g];
+    }
+    const int64_t ns = (int64_t)rank_id.size();
+    for (int64_t r = 0; r < ns; ++r) rank_of[rank_id[r]] = (int32_t)r;
+    std::vector<int32_t> seg(ns + 1, 0), pos(std::max<int64_t>(ns, 1)), idx(std::max<int64_t>(npts, 1)),
+        brank(std::max<int64_t>(npts, 1)), rank_pt(std::max<int64_t>(npts, 1));
+    std::vector<double> c2(std::max<int64_t>(ns, 1));
+    for (int64_t r = 0; r < ns; ++r) {
+        seg[r + 1] = seg[r] + cnt[rank_id[r]];
+        pos[r] = seg[r];
+        c2[r] = pseudo ? 0.0 : h_c[rank_id[r]] * h_c[rank_id[r]];
+    }
+    for (int64_t i = 0; i < npts; ++i) {
+        const int32_t r = rank_of[eid(perm[i])];
+        rank_pt[i] = r;
+        const int32_t k = pos[r]++;
+        idx[k] = (int32_t)i;
+        brank[k] = r;
+    }
+    const int64_t nchunk = (npts + BIAS_CHUNK - 1) / BIAS_CHUNK;
+    std::vector<int32_t> sbase(std::max<int64_t>(nchunk, 1));
+    int64_t nslots = 0, npts3 = 0, nslots3 = 0;
+    for (int64_t c = 0; c < nchunk; ++c) {
+        const int64_t kb = std::min(npts, (c + 1) * BIAS_CHUNK);
+        const int32_t ra = brank[c * BIAS_CHUNK], rb = brank[kb - 1];
+        sbase[c] = (int32_t)(nslots - ra);
+        nslots += rb - ra + 1;
+        if (ra < nsr) {
+            npts3 += kb - c * BIAS_CHUNK;
+            nslots3 += rb - ra + 1;
+        }
+    }
+    std::vector<int32_t> long_rank, long_of(std::max<int64_t>(ns, 1), -1);
+    for (int64_t r = 0; r < ns; ++r)
+        if ((seg[r + 1] - 1) / BIAS_CHUNK - seg[r] / BIAS_CHUNK + 1 > BIAS_LONG) {
+            long_of[r] = (int32_t)long_rank.size();
+            long_rank.push_back((int32_t)r);
+        }
+    BiasData& B = S.bias;
+    B.nb = nb; B.ns = ns; B.npts = npts; B.nchunk = nchunk; B.nslots = nslots;
+    B.nlong = (int64_t)long_rank.size();
+    const int nch = h_grp ? 3 : 1;
+    B.lsum.alloc(std::max<int64_t>(B.nlong, 1) * nch);
+    B.nbk = grid_for(ns, BLOCK, BIAS_NPART);
+    auto up = [&](DBuf<int32_t>& d, const std::vector<int32_t>& h) {
+        d.alloc((int64_t)h.size());
+        d.upload(h.data(), (int64_t)h.size(), S.stream);
+    };
+    auto upd = [&](DBuf<double>& d, const std::vector<double>& h) {
+        d.alloc((int64_t)h.size());
+        d.upload(h.data(), (int64_t)h.size(), S.stream);
+    };
+    up(B.idx, idx); up(B.brank, brank); up(B.rank_pt, rank_pt); up(B.seg, seg); up(B.sbase, sbase);
+    up(B.long_of, long_of);
+    long_rank.resize(std::max<size_t>(long_rank.size(), 1));
+    up(B.long_rank, long_rank);
+    rank_id.resize(std::max<int64_t>(ns, 1));
+    up(B.rank_id, rank_id);
+    upd(B.c2, c2);
+    B.w2.alloc(std::max<int64_t>(npts, 1));
+    B.D.alloc(std::max<int64_t>(ns, 1));
+    B.sD.alloc(std::max<int64_t>(ns, 1));
+    B.slots.alloc(std::max<int64_t>(nslots, 1) * nch);
+    B.bval.alloc(std::max<int64_t>(nb, 1));
+    std::vector<double> u, gc2;
+    if (h_grp) {
+        B.ng = ng; B.nsr = nsr; B.npts3 = npts3; B.nslots3 = nslots3; B.pseudo = pseudo;
+        B.nrk = grid_for(ns, BLOCK, BIAS_NPART / 2);
+        B.ngk = grid_for(ng, BLOCK / 64, BIAS_NPART / 2);
+        B.nbk = B.nrk + B.ngk;
+        u.assign(2 * std::max<int64_t>(npts, 1), 0.0);
+        for (int64_t i = 0; i < npts; ++i)
+            if (h_grp[perm[i]] >= 0) {
+                u[2 * i] = h_u[2 * (int64_t)perm[i]];
+                u[2 * i + 1] = h_u[2 * (int64_t)perm[i] + 1];
+            }
+        gc2.resize(2 * ng);
+        for (int64_t k = 0; k < 2 * ng; ++k) gc2[k] = h_gc[k] * h_gc[k];
+        rgrp.resize(std::max<int64_t>(nsr, 1));
+        up(B.gseg, gseg); up(B.rgrp, rgrp);
+        upd(B.u, u); upd(B.gc2, gc2);
+        B.rsum.alloc(3 * std::max<int64_t>(ns, 1));
+        B.e.alloc(2 * std::max<int64_t>(ns, 1));
+        B.F.alloc(3 * ng); B.L.alloc(3 * ng); B.gam.alloc(2 * ng); B.gval.alloc(2 * ng);
+        B.tmp.alloc(std::max<int64_t>(npts, 1));
+    }
+    HIP_CHECK(hipStreamSynchronize(S.stream));   // the uploads read host vectors of this scope
+    B.h_id = std::move(keep_id);
+    B.h_c = std::move(keep_c);
+    B.h_grp = std::move(keep_grp);
+    B.on = npts > 0 && ns > 0;   // no data rows: every bias is 0, the operator is unchanged
+}
+}  // namespace
+
+// id: the data rows' bias IDs in the caller's row order; c: 1 / E_bias per ID.  Clears the slopes.
 void bias_set(System& S, int64_t npts, const int32_t* h_id, int64_t nb, const double* h_c) {
     if (!S.mf || S.dist) throw std::invalid_argument("lsq_set_data_bias: needs a single-GPU structured system (lsq_set_matrix_stencil)");
     if (npts != S.mfh.npts) throw std::invalid_argument("lsq_set_data_bias: npts differs from the system's data rows");
@@ -2816,83 +3003,66 @@ void bias_set(System& S, int64_t npts, const int32_t* h_id, int64_t nb, const do
                        dc.p, flag.p);
     KERNEL_CHECK();
     int hf = 0;
-    std::vector<int32_t> perm(npts);
     flag.download(&hf, 1, S.stream);
-    S.dmf_perm.download(perm.data(), npts, S.stream);
     HIP_CHECK(hipStreamSynchronize(S.stream));
     if (hf & 1) throw std::invalid_argument("lsq_set_data_bias: a bias ID lies outside [0, nb)");
     if (hf & 2) throw std::invalid_argument("lsq_set_data_bias: every c must be > 0");
-    bias_clear(S);
-    graph_cache_drop(&S);   // captured iterations hold no elimination step yet
-    S.cg_ready = false;
-    // ranks: the IDs that carry points, in ID order; the sorted points indexed stably by rank
-    std::vector<int32_t> cnt(nb + 1, 0), rank_of(nb, -1), rank_id;
-    for (int64_t i = 0; i < npts; ++i) ++cnt[h_id[i]];
-    for (int64_t j = 0; j < nb; ++j)
-        if (cnt[j]) {
-            rank_of[j] = (int32_t)rank_id.size();
-            rank_id.push_back((int32_t)j);
-        }
-    const int64_t ns = (int64_t)rank_id.size();
-    std::vector<int32_t> seg(ns + 1, 0), pos(std::max<int64_t>(ns, 1)), idx(std::max<int64_t>(npts, 1)),
-        brank(std::max<int64_t>(npts, 1)), rank_pt(std::max<int64_t>(npts, 1));
-    std::vector<double> c2(std::max<int64_t>(ns, 1));
-    for (int64_t r = 0; r < ns; ++r) {
-        seg[r + 1] = seg[r] + cnt[rank_id[r]];
-        pos[r] = seg[r];
-        c2[r] = h_c[rank_id[r]] * h_c[rank_id[r]];
-    }
-    for (int64_t i = 0; i < npts; ++i) {
-        const int32_t r = rank_of[h_id[perm[i]]];
-        rank_pt[i] = r;
-        const int32_t k = pos[r]++;
-        idx[k] = (int32_t)i;
-        brank[k] = r;
-    }
-    const int64_t nchunk = (npts + BIAS_CHUNK - 1) / BIAS_CHUNK;
-    std::vector<int32_t> sbase(std::max<int64_t>(nchunk, 1));
-    int64_t nslots = 0;
-    for (int64_t c = 0; c < nchunk; ++c) {
-        const int32_t ra = brank[c * BIAS_CHUNK], rb = brank[std::min(npts, (c + 1) * BIAS_CHUNK) - 1];
-        sbase[c] = (int32_t)(nslots - ra);
-        nslots += rb - ra + 1;
-    }
-    std::vector<int32_t> long_rank, long_of(std::max<int64_t>(ns, 1), -1);
-    for (int64_t r = 0; r < ns; ++r)
-        if ((seg[r + 1] - 1) / BIAS_CHUNK - seg[r] / BIAS_CHUNK + 1 > BIAS_LONG) {
-            long_of[r] = (int32_t)long_rank.size();
-            long_rank.push_back((int32_t)r);
-        }
-    BiasData& B = S.bias;
-    B.nb = nb; B.ns = ns; B.npts = npts; B.nchunk = nchunk; B.nslots = nslots;
-    B.nlong = (int64_t)long_rank.size();
-    B.lsum.alloc(std::max<int64_t>(B.nlong, 1));
-    B.nbk = grid_for(ns, BLOCK, BIAS_NPART);
-    auto up = [&](DBuf<int32_t>& d, const std::vector<int32_t>& h) {
-        d.alloc((int64_t)h.size());
-        d.upload(h.data(), (int64_t)h.size(), S.stream);
-    };
-    up(B.idx, idx); up(B.brank, brank); up(B.rank_pt, rank_pt); up(B.seg, seg); up(B.sbase, sbase);
-    up(B.long_of, long_of);
-    long_rank.resize(std::max<size_t>(long_rank.size(), 1));
-    up(B.long_rank, long_rank);
-    rank_id.resize(std::max<int64_t>(ns, 1));
-    up(B.rank_id, rank_id);
-    B.c2.alloc((int64_t)c2.size());
-    B.c2.upload(c2.data(), (int64_t)c2.size(), S.stream);
-    B.w2.alloc(std::max<int64_t>(npts, 1));
-    B.D.alloc(std::max<int64_t>(ns, 1));
-    B.sD.alloc(std::max<int64_t>(ns, 1));
-    B.slots.alloc(std::max<int64_t>(nslots, 1));
-    B.bval.alloc(nb);
-    HIP_CHECK(hipStreamSynchronize(S.stream));
-    B.on = npts > 0 && ns > 0;   // no data rows: every bias is 0, the operator is unchanged
+    bias_build(S, npts, h_id, nb, h_c, nullptr, nullptr, 0, nullptr);
 }
 
-// the biases of the x in S.cg_x (full space) for the right-hand side dbp: b_j = Σ W²(d − A_d x) / D_j
+// the slopes cleared: the bias-only layout again (bit for bit the one lsq_set_data_bias made), or nothing
+void slope_clear(System& S) {
+    if (!S.bias.ng) return;
+    if (!S.bias.nb) {
+        bias_clear(S);
+        return;
+    }
+    const std::vector<int32_t> id = S.bias.h_id;
+    const std::vector<double> c = S.bias.h_c;
+    bias_build(S, (int64_t)id.size(), id.data(), (int64_t)c.size(), c.data(), nullptr, nullptr, 0, nullptr);
+}
+
+// grp: the data rows' slope groups (−1: none) in the caller's row order, u: two coefficients per row,
+// c: two constraint weights per group
+void slope_set(System& S, int64_t npts, const int32_t* h_grp, const double* h_u, int64_t ng, const double* h_c) {
+    if (!S.mf || S.dist) throw std::invalid_argument("lsq_set_data_slope: needs a single-GPU structured system (lsq_set_matrix_stencil)");
+    if (npts != S.mfh.npts) throw std::invalid_argument("lsq_set_data_slope: npts differs from the system's data rows");
+    if (ng >= (int64_t)INT32_MAX - 1) throw std::invalid_argument("lsq_set_data_slope: too many slope groups");
+    if (!S.dmf.ok || S.dmf.npts != npts)
+        throw std::invalid_argument("lsq_set_data_slope: needs matrix-free data rows (interpolation grids on one (y, x) lattice)");
+    for (int64_t k = 0; k < 2 * ng; ++k)
+        if (!(h_c[k] > 0.0)) throw std::invalid_argument("lsq_set_data_slope: every c must be > 0");
+    const int64_t nb = S.bias.nb;
+    std::vector<int32_t> sgrp(nb, -1);   // nested: the rows of a bias ID lie in at most one group
+    for (int64_t i = 0; i < npts; ++i) {
+        const int32_t g = h_grp[i];
+        if (g < -1 || g >= ng) throw std::invalid_argument("lsq_set_data_slope: a slope group lies outside {-1} and [0, ng)");
+        if (g < 0) continue;
+        if (!std::isfinite(h_u[2 * i]) || !std::isfinite(h_u[2 * i + 1]))
+            throw std::invalid_argument("lsq_set_data_slope: a coefficient u is not finite");
+        if (nb) {
+            int32_t& sg = sgrp[S.bias.h_id[i]];
+            if (sg >= 0 && sg != g)
+                throw std::invalid_argument("lsq_set_data_slope: the layout is not nested (the rows of a bias ID lie in "
+                                            "more than one slope group)");
+            sg = g;
+        }
+    }
+    if (nb) {
+        const std::vector<int32_t> id = S.bias.h_id;
+        const std::vector<double> c = S.bias.h_c;
+        bias_build(S, npts, id.data(), nb, c.data(), h_grp, h_u, ng, h_c);
+    } else {
+        bias_build(S, npts, nullptr, 0, nullptr, h_grp, h_u, ng, h_c);
+    }
+}
+
+// the biases (and slopes) of the x in S.cg_x (full space) for the right-hand side dbp:
+// [b; γ] = M⁻¹ Zᵀ W² (d − A_d x); without slopes b_j = Σ W²(d − A_d x) / D_j
 void bias_values(System& S, const double* dbp) {
     BiasData& B = S.bias;
     B.bval.zero(S.stream);
+    if (B.ng) B.gval.zero(S.stream);
     if (bias_active(S)) {
         const CgGrids g = cg_grids(S, 1);
         DBuf<CgState> st(1);
@@ -2902,12 +3072,16 @@ void bias_values(System& S, const double* dbp) {
         hipLaunchKernelGGL(k_bias_resid, dim3(grid_for(B.npts)), dim3(BLOCK), 0, S.stream, B.npts, S.dmf_perm.p, B.w2.p,
                            dbp, S.cg_t.p, S.cg_t.p);
         bias_launch_reduce(S, nullptr, S.cg_t.p, nullptr);
-        hipLaunchKernelGGL(k_bias_scatter, dim3(grid_for(B.ns)), dim3(BLOCK), 0, S.stream, B.ns, B.rank_id.p, B.sD.p,
-                           B.bval.p);
+        if (!B.pseudo)
+            hipLaunchKernelGGL(k_bias_scatter, dim3(grid_for(B.ns)), dim3(BLOCK), 0, S.stream, B.ns, B.rank_id.p, B.sD.p,
+                               B.bval.p);
+        if (B.ng)
+            HIP_CHECK(hipMemcpyAsync(B.gval.p, B.gam.p, 2 * B.ng * sizeof(double), hipMemcpyDeviceToDevice, S.stream));
         KERNEL_CHECK();
         HIP_CHECK(hipStreamSynchronize(S.stream));
     }
     B.solved = true;
+    B.gsolved = B.ng > 0;
 }
 
 void bias_get(System& S, double* h_b) {
@@ -2917,14 +3091,22 @@ void bias_get(System& S, double* h_b) {
     HIP_CHECK(hipStreamSynchronize(S.stream));
 }
 
-// why a solve with biases set cannot run (empty: it can)
+void slope_get(System& S, double* h_g) {
+    if (!S.bias.ng) throw std::invalid_argument("lsq_get_data_slope: no slopes set");
+    if (!S.bias.gsolved) throw std::invalid_argument("lsq_get_data_slope: no lsq_solve since the slopes were set");
+    S.bias.gval.download(h_g, 2 * S.bias.ng, S.stream);
+    HIP_CHECK(hipStreamSynchronize(S.stream));
+}
+
+// why a solve with biases or slopes set cannot run (empty: it can)
 std::string bias_refusal(System& S, int method, int precond) {
-    if (!S.bias.nb) return "";
-    if (S.dist) return "data biases run on single-GPU handles only";
-    if (method != 1) return "data biases need CGNR (method 1)";
-    if (precond != 1 && precond != 3 && precond != 4) return "data biases run with precond 1, 3 or 4";
-    if (!cg_available(S, precond)) return "data biases need the structured CGNR operator: " + (S.cg_ok ? S.mg_why : S.cg_why);
-    if (!cg_use_dmf(S)) return "data biases need the matrix-free column-mode CGNR data rows (tile mode is not covered)";
+    if (!S.bias.nb && !S.bias.ng) return "";
+    const std::string what = S.bias.nb ? "data biases" : "data slopes";
+    if (S.dist) return what + " run on single-GPU handles only";
+    if (method != 1) return what + " need CGNR (method 1)";
+    if (precond != 1 && precond != 3 && precond != 4) return what + " run with precond 1, 3 or 4";
+    if (!cg_available(S, precond)) return what + " need the structured CGNR operator: " + (S.cg_ok ? S.mg_why : S.cg_why);
+    if (!cg_use_dmf(S)) return what + " need the matrix-free column-mode CGNR data rows (tile mode is not covered)";
     return "";
 }
 

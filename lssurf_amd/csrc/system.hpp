@@ -333,6 +333,34 @@ struct BiasData {
     DBuf<double> sD;                // rank -> s / D of the last reduction
     DBuf<double> slots;
     DBuf<double> bval;              // ID -> bias of the last solve
+    std::vector<int32_t> h_id;      // the caller's IDs and c: clearing the slopes rebuilds the bias-only layout
+    std::vector<double> h_c;
+    // Slope biases (lsq_set_data_slope; slope.inc): every row of slope group s carries two further
+    // eliminated columns with the coefficients u_i.  Every rank's rows lie in at most one group
+    // ("nested"), so the eliminated block reduces to one 2 × 2 system per group.  With slopes set the
+    // ranks are ordered by (group, ID), the ranks outside every group last: the ranks of a group are
+    // one range, the chunks that start below nsr sum three channels (src, src·u₀, src·u₁) into three
+    // planes of slots, and a wave per group adds its ranks' sums in rank order.  Without biases
+    // (pseudo) the ranks are one pseudo-ID per group and one for the rows outside: they only carry
+    // the sums, their β is 0.
+    int64_t ng = 0;                 // slope groups (0: no slopes)
+    int64_t nsr = 0;                // ranks inside a group: ranks [0, nsr)
+    int64_t npts3 = 0, nslots3 = 0; // points and slots of the three-channel chunks (byte model)
+    bool pseudo = false;
+    bool gsolved = false;           // gval belongs to the last lsq_solve's x
+    int nrk = 0, ngk = 0;           // workgroups (= partials) of the per-rank and the per-group kernel: nbk = nrk + ngk
+    DBuf<int32_t> gseg;             // group -> first rank (ng + 1)
+    DBuf<int32_t> rgrp;             // rank -> group (nsr)
+    DBuf<double> u;                 // sorted point -> (u₀, u₁); 0 for a row outside every group
+    DBuf<double> gc2;               // group -> (c₀², c₁²)
+    DBuf<double> rsum;              // 3 × ns: the ranks' channel sums of the last reduction
+    DBuf<double> e;                 // 2 × ns: e_j = Σ w² u (per solve)
+    DBuf<double> F;                 // group -> Σ w² (u₀u₀, u₀u₁, u₁u₁) (per solve)
+    DBuf<double> L;                 // group -> Cholesky factor (l₀₀, l₁₀, l₁₁) of G_s (per solve)
+    DBuf<double> gam;               // group -> γ of the last reduction
+    DBuf<double> tmp;               // sorted point -> w² u_k (per solve)
+    DBuf<double> gval;              // group -> slopes of the last solve
+    std::vector<int32_t> h_grp;     // the caller's groups (empty: none)
 };
 
 // Extra sparse rows behind the stencil rows (lsq_set_extra_rows; xrows.inc): ≤ XR_MAXW entries per

@@ -19,6 +19,7 @@ The dz priors (prior_args, prior_edge_args; match_priors.py) take in-memory grid
 last in Gc and the device carries them as extra rows inside matrix-free CGNR (lsq_set_extra_rows).
 With priors compute_E, n_gpus > 1 and lsq_bias='eliminate' raise NotImplementedError.
 lsq_prior_mg=True lets the multigrid preconditioner (precond 4) carry them, lumped into its coarse levels.
+Slope biases (data_slope_sensors) go with the data biases: they need bias_params and lsq_bias.
 Data biases (bias_params) run when the solver key lsq_bias says how: 'eliminate' (the device
 eliminates them inside CGNR, lsq_set_data_bias), 'columns' (ordinary columns of a generic system)
 or 'auto' (with priors: 'columns', with a warning where it would have eliminated).
@@ -29,6 +30,7 @@ import warnings
 import numpy as np
 
 from . import containers as pc
+from .data_slope_bias import RESCALE as SLOPE_RESCALE, data_slope_bias, slope_columns
 from .bias_functions import assign_bias_ID, bias_expected, edit_by_bias, parse_biases, setup_bias_fit
 from .calc_sigma_extra import RDE, calc_sigma_extra, calc_sigma_extra_on_grid
 from .constraint_functions import build_reference_epoch_matrix, node_column_blocks, \
@@ -79,6 +81,9 @@ class FitSystem:
         """bias = (ids, c): eliminated data biases (LSQSolver.set_data_bias) — G_data and Gc are then
         the grid-only operators, the caller's row weights and rhs may carry further (bias
         constraint) rows behind them, and the biases take the columns after n_full in expand().
+        bias = (ids, c, (group, u, c_slope)): slope biases too (LSQSolver.set_data_slope): group per
+        data row (−1: none), u (rows, 2), c_slope (groups, 2); their values follow the biases in
+        expand(), and their constraint rows follow the bias constraint rows on the host.
         extra_ops: the operators behind Gc's last rows that are neither interpolation nor stencil
         rows (the priors of match_priors).  With a structured description of the other rows they
         are staged as the device's extra rows (LSQSolver.set_extra_rows) and matrix-free CGNR
@@ -172,6 +177,7 @@ class FitSystem:
         self.mg_build_s = 0.0
         self.stats = None
         self.bias_ids, self.bias_vals = None, None
+        self.slope_grp, self.slope_u, self.slope_vals = None, None, None
         if bias is not None:
             # only matrix-free CGNR carries the eliminated biases: never the dense preconditioner
             # (LSQR), whatever the size.  'auto' then takes the node-block preconditioner: the multigrid
@@ -179,10 +185,16 @@ class FitSystem:
             # block-Jacobi costs 1.6–2× (profiles/bias_c4.json)
             self.dense_ok = False
             try:
-                ids, c = bias
+                ids, c = bias[:2]
                 self.bias_ids = np.asarray(ids).astype(np.int32)
                 self.solver.set_data_bias(self.bias_ids, c)
                 self.bias_vals = np.zeros(np.size(c))
+                if len(bias) > 2 and bias[2] is not None:
+                    grp, u, cs = bias[2]
+                    self.slope_grp = np.asarray(grp).astype(np.int32)
+                    self.slope_u = np.asarray(u, dtype=float).reshape(-1, 2)
+                    self.solver.set_data_slope(self.slope_grp, self.slope_u, cs)
+                    self.slope_vals = np.zeros((np.size(cs) // 2, 2))
             except Exception:
                 self.solver.close()
                 raise
@@ -231,12 +243,17 @@ class FitSystem:
         x, self.stats = self.solver.solve(rhs, x0=x0, b_rows=getattr(self, 'b_rows', 0), **opts)
         if self.bias_ids is not None:
             self.bias_vals = self.solver.data_bias()
+        if self.slope_grp is not None:
+            self.slope_vals = self.solver.data_slope()
         return x
 
     def expand(self, x):
         if self.bias_ids is not None:   # the biases of the last solve, in the columns after the grids
-            m0 = np.zeros(self.n_full + self.bias_vals.size)
-            m0[self.n_full:] = self.bias_vals
+            n_slope = 0 if self.slope_grp is None else self.slope_vals.size
+            m0 = np.zeros(self.n_full + self.bias_vals.size + n_slope)
+            m0[self.n_full:self.n_full + self.bias_vals.size] = self.bias_vals
+            if n_slope:   # behind the biases, (x, y) per group
+                m0[self.n_full + self.bias_vals.size:] = self.slope_vals.ravel()
         else:
             m0 = np.zeros(self.n_full)
         m0[self.keep_cols] = x
@@ -248,6 +265,9 @@ class FitSystem:
         y = self.solver.spmv_rows(x, 0, self.n_data)
         if self.bias_ids is not None:
             y += self.bias_vals[self.bias_ids]
+        if self.slope_grp is not None:
+            on = self.slope_grp >= 0
+            y[on] += np.sum(self.slope_u[on] * self.slope_vals[self.slope_grp[on]], axis=1)
         return y
 
     def rows_sumsq(self, x, ranges):
@@ -626,14 +646,16 @@ def _bias_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, bias_model, m
     rows are a prefix of the host rows); 'columns': the biases as ordinary columns of a generic
     (COO-formed) system; 'auto': 'columns' when the grid unknowns (the eliminating system's columns)
     are few enough for the dense preconditioner, when the options ask for what only 'columns' runs
-    (LSQR, the dense preconditioner) or when the device cannot eliminate (no matrix-free data rows),
-    else 'eliminate'.
+    (LSQR, the dense preconditioner) or when the device cannot eliminate (no matrix-free data rows, or
+    slope groups that the bias IDs do not nest in), else 'eliminate'.  Slope biases (slope_bias_dict
+    of bias_model) go with the biases either way.
     With prior_ops (the priors behind the bias constraint rows of Gc) only 'columns' runs: the device
     rows of 'eliminate' are a prefix of the host rows, which rows behind the bias constraints would
     break.  smooth_fit refuses 'eliminate' with priors; 'auto' takes 'columns' and warns where it
     would have eliminated, since the generic system costs the memory and speed of matrix-free CGNR."""
     n_grid = G_grid.col_N if G_grid is not None else None
-    n_bias = int(G_data.col_N) - int(n_grid) if n_grid is not None else 0
+    slope_dict = bias_model.get('slope_bias_dict', {})
+    n_bias = int(G_data.col_N) - int(n_grid) - 2 * len(slope_dict) if n_grid is not None else 0
     if mode == 'auto' and (describe(G_grid, Gc_grid, with_fields=True) is None or
                            np.count_nonzero(keep_cols < n_grid) <= args['lsq_dense_max'] or
                            args['lsq_method'] == 'lsqr' or args['lsq_precond'] == 2):
@@ -646,9 +668,13 @@ def _bias_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, bias_model, m
     if mode != 'columns':
         ids = np.asarray(data.bias_ID).astype(np.int32)
         c = 1. / bias_expected(bias_model, n_bias)
+        bias = (ids, c)
+        if slope_dict:   # the groups in the order of their columns
+            _, group, u = slope_columns(data, np.array(list(slope_dict.keys())))
+            bias += ((group, u, np.full((len(slope_dict), 2), 1. / (bias_model['E_slope_bias'] * SLOPE_RESCALE))),)
         try:
             return FitSystem(G_grid, Gc_grid, keep_cols[keep_cols < n_grid], n_grid, device=device, grids=grids,
-                             bias=(ids, c))
+                             bias=bias)
         except NativeError:
             if mode == 'eliminate':
                 raise
@@ -665,8 +691,16 @@ def smooth_fit(**kwargs):
     for key in OUT_OF_SCOPE:
         if args.get(key) is not None:
             raise NotImplementedError(f'smooth_fit: {key!r} is outside lssurf_amd (SURVEY.md §2)')
-    if args.get('data_slope_sensors') is not None and len(args['data_slope_sensors']) > 0:
-        raise NotImplementedError("smooth_fit: 'data_slope_sensors' is outside lssurf_amd")
+    has_slopes = args.get('data_slope_sensors') is not None and len(args['data_slope_sensors']) > 0
+    if has_slopes:
+        # slope biases are eliminated (or carried as columns) with the data biases: the same key says how,
+        # and every refusal of bias_params below holds for them
+        if args['lsq_bias'] is None:
+            raise NotImplementedError("smooth_fit: 'data_slope_sensors' needs the solver key lsq_bias ('eliminate', "
+                                      "'columns' or 'auto'); without it slope biases are outside lssurf_amd")
+        if args['bias_params'] is None:
+            raise ValueError("smooth_fit: 'data_slope_sensors' needs 'bias_params' (the model's biases are read "
+                             "back through them)")
     if not isinstance(args['lsq_prior_mg'], (bool, np.bool_)):
         raise ValueError(f"smooth_fit: lsq_prior_mg must be True or False, not {args['lsq_prior_mg']!r}")
     bias_mode = args['lsq_bias']
@@ -758,6 +792,19 @@ def smooth_fit(**kwargs):
         zero_prior.add(constraint_op_list[-1].name)
         if args['bias_nsigma_edit']:
             bias_model['bias_param_dict']['edited'] = np.zeros_like(bias_model['bias_param_dict']['ID'], dtype=bool)
+    # slope biases: two columns per listed sensor that the valid data hold, behind the bias columns, and
+    # their constraint rows behind the bias constraint rows (smooth_fit.py:515-525)
+    if has_slopes:
+        sensors = np.asarray(args['data_slope_sensors'])
+        args['data_slope_sensors'] = sensors[np.isin(sensors, data.sensor)]
+        if len(args['data_slope_sensors']) > 0:
+            bias_model['E_slope_bias'] = args['E_slope_bias']
+            G_slope, Gc_slope, bias_model = data_slope_bias(data, bias_model, sensors=args['data_slope_sensors'],
+                                                            col_0=G_data.col_N, E_rms_bias=args['E_slope_bias'])
+            if G_slope is not None:
+                G_data.add(G_slope)
+                constraint_op_list.append(Gc_slope)
+                zero_prior.add(Gc_slope.name)
     # priors, in the reference's order (smooth_fit.py:575-582), behind every other constraint
     prior_ops = []
     if args.get('prior_args') is not None:

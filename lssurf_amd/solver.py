@@ -28,6 +28,7 @@ class LSQSolver:
         self.device = device
         self.m = self.n = self.n_full = None
         self._n_bias = 0           # bias IDs set by set_data_bias
+        self._n_slope = 0          # slope groups set by set_data_slope
 
     # ---- lifetime --------------------------------------------------------------------------
     def close(self):
@@ -290,21 +291,58 @@ class LSQSolver:
         """One additive bias per ID on the data rows, eliminated inside CGNR (lsq_set_data_bias).
 
         ids: the bias ID of every data row (caller's row order), in [0, len(c)); c: 1 / expected
-        bias size per ID, > 0.  ids = None (or an empty c) clears the biases."""
+        bias size per ID, > 0.  ids = None (or an empty c) clears the biases.  Setting or clearing
+        the biases clears the slopes of set_data_slope."""
         if ids is None or c is None or np.size(c) == 0:
             self._check(self._L.lsq_set_data_bias(self._h, 0, None, 0, None), 'lsq_set_data_bias')
-            self._n_bias = 0
+            self._n_bias = self._n_slope = 0
             return
         ids = as_c(ids, np.int32)
         c = as_c(c, np.float64)
         self._check(self._L.lsq_set_data_bias(self._h, ids.size, ptr(ids), c.size, ptr(c)), 'lsq_set_data_bias')
         self._n_bias = int(c.size)
+        self._n_slope = 0
 
     def data_bias(self):
         """The biases that belong to the last solve's x (one per ID)."""
         b = np.zeros(max(self._n_bias, 1))
         self._check(self._L.lsq_get_data_bias(self._h, ptr(b)), 'lsq_get_data_bias')
         return b[:self._n_bias]
+
+    def set_data_slope(self, grp, u, c):
+        """Two slope unknowns per group on the data rows, eliminated with the biases
+        (lsq_set_data_slope); call after set_data_bias.
+
+        grp: the slope group of every data row (caller's row order), −1 for none, else in
+        [0, len(c) / 2); u: (rows, 2) coefficients, read where grp ≥ 0; c: (groups, 2), 1 / expected
+        slope size, > 0.  The rows of a bias ID must lie in at most one group.  grp = None (or an
+        empty c) clears the slopes and keeps the biases."""
+        if grp is None or u is None or c is None or np.size(c) == 0:
+            self._check(self._L.lsq_set_data_slope(self._h, 0, None, None, 0, None), 'lsq_set_data_slope')
+            self._n_slope = 0
+            return
+        grp = as_c(grp, np.int32)
+        u = as_c(u, np.float64)
+        c = as_c(c, np.float64)
+        if u.size != 2 * grp.size or c.size % 2:
+            raise ValueError('set_data_slope: u must hold two values per row and c two per group')
+        self._check(self._L.lsq_set_data_slope(self._h, grp.size, ptr(grp), ptr(u), c.size // 2, ptr(c)),
+                    'lsq_set_data_slope')
+        self._n_slope = int(c.size // 2)
+
+    def data_slope(self):
+        """The slopes that belong to the last solve's x: (groups, 2)."""
+        g = np.zeros(max(2 * self._n_slope, 1))
+        self._check(self._L.lsq_get_data_slope(self._h, ptr(g)), 'lsq_get_data_slope')
+        return g[:2 * self._n_slope].reshape(-1, 2)
+
+    def profile_data_slope(self, reps=10, precond=3):
+        """Per-kernel times of the slope elimination inside real iterations of the live iterate()
+        state: {name: (ms, algorithmic bytes)} for the chunk pass, the per-rank sums, the per-group
+        kernel and the apply pass (lsq_profile_data_slope)."""
+        o = np.zeros(8)
+        self._check(self._L.lsq_profile_data_slope(self._h, int(reps), int(precond), ptr(o)), 'lsq_profile_data_slope')
+        return {k: (float(o[i]), float(o[4 + i])) for i, k in enumerate(('chunk', 'rank', 'group', 'apply'))}
 
     def info(self):
         o = np.zeros(8, np.int64)
