@@ -531,6 +531,46 @@ int lsq_get_data_slope(lsq_handle* h, double* g);
  * per-rank sums, of the per-group kernel, of the apply pass, and the algorithmic HBM bytes of each}.
  * −2 without such a state or without slopes in the operator. */
 int lsq_profile_data_slope(lsq_handle* h, int32_t reps, int32_t precond, double* out8);
+
+/* Sensor bias grids: the data rows of grid s gain the unknowns a_s, a coarse 2-D grid of additive bias
+ * (smooth_fit's sensor_grid_bias_params), through the bilinear weights wt[4i .. 4i + 3] on the nodes
+ * node[4i .. 4i + 3] (local to the grid; a weight of 0 pads a dropped corner), and the grid is held by
+ * constraint rows C_s a_s = 0.  A row lies in one grid and C_s touches its own nodes only, so with
+ * B the interpolation columns and M = BᵀW²B + K, K_s = C_sᵀC_s, the normal operator is
+ * AᵀA − A_dᵀ W² B M⁻¹ Bᵀ W² A_d with one dense SPD block M_s per grid (x keeps its length).
+ * lsq_set_sensor_grids: call after lsq_set_matrix_stencil.  grid[i] ∈ {−1} ∪ [0, ng) for data row i in
+ * the caller's row order; node and wt are read only where grid ≥ 0.  K_s, already weighted and constant
+ * over the outer iterations, is passed as the triplets k_ptr[s] … k_ptr[s + 1] (local rows and columns,
+ * both triangles, duplicates summed in their order; k_ptr null: no K).  ng = 0 or a null pointer clears
+ * the grids, and the handle then solves bit for bit as if none had been set.  Returns −2 with the handle
+ * unchanged on a grid or node out of range, a weight or value that is not finite, a wrong npts, data
+ * biases or slopes already set (lsq_set_data_bias / lsq_set_data_slope likewise return −2 while grids
+ * are set), a node that shares rows with more than 9 nodes (the rows must be cells of a lattice), or a
+ * grid over the size cap: at most LSQ_SGRID_MAX_NODES nodes per grid and LSQ_SGRID_MAX_FACTOR_BYTES for
+ * all inverse factors together (each npad², npad = nodes rounded up to 64; the device holds two such
+ * sets).  Every CG step reads each grid's inverse factor once: 8·npad² bytes, 32 MB at 2048 nodes, about
+ * 10 µs of HBM time; all factors at the byte cap cost 0.3 ms per step, three quarters of an iteration of
+ * a 2 M-point fit, beyond which the grids are better carried as ordinary columns.
+ * Solves, lsq_cg_available and lsq_normal_apply follow the rules of the data biases above: method 1,
+ * precond 1, 3 or 4, one GPU.  M_s is assembled and factored at the start of every solve for the
+ * current weights and mask; a pivot that is not positive (below 1e-12 of its diagonal entry) makes
+ * lsq_solve return −2 with a message that names the grid — a grid held by its curvature only whose
+ * kept data do not pin its bilinear null space.  Every sum runs in a fixed order without atomics:
+ * results are bitwise equal run to run.
+ * lsq_get_sensor_grids: the node values a (grid after grid, Σ n_nodes) that belong to the last
+ * lsq_solve's x; −2 before any solve. */
+#define LSQ_SGRID_MAX_NODES 2048
+#define LSQ_SGRID_MAX_FACTOR_BYTES (1ll << 30)
+int lsq_set_sensor_grids(lsq_handle* h, int64_t npts, const int32_t* grid /* −1: none */,
+                         const int32_t* node /* 4 per row, local to the grid */, const double* wt /* 4 per row */,
+                         int32_t ng, const int64_t* n_nodes, const int64_t* k_ptr, const int32_t* k_row,
+                         const int32_t* k_col, const double* k_val);
+int lsq_get_sensor_grids(lsq_handle* h, double* a);
+/* The sensor grids' kernels timed inside reps real iterations of the live lsq_iterate state (method 1,
+ * this precond; HIP events between the launches): out8 = {ms of s = Bᵀ td, of z = R⁻ᵀ s, of y = R⁻¹ z,
+ * of the apply pass, and the algorithmic HBM bytes of each}.  −2 without such a state or without grids
+ * in the operator. */
+int lsq_profile_sensor_grids(lsq_handle* h, int32_t reps, int32_t precond, double* out8);
 int lsq_sell_info(lsq_handle* h, int64_t* out8);
 
 /* ---- triangular kernels (replace the Cython kernels; R upper triangular CSR, int32 indices,

@@ -25,6 +25,12 @@ void slope_set(System& S, int64_t npts, const int32_t* h_grp, const double* h_u,
 void slope_clear(System& S);
 void slope_get(System& S, double* h_g);
 void cg_profile_slope(System& S, int reps, int precond, double* out8);
+void sgrid_set(System& S, int64_t npts, const int32_t* h_grid, const int32_t* h_node, const double* h_wt, int64_t ng,
+               const int64_t* h_nn, const int64_t* k_ptr, const int32_t* k_row, const int32_t* k_col,
+               const double* k_val);
+void sgrid_clear(System& S);
+void sgrid_get(System& S, double* h_a);
+void cg_profile_sgrid(System& S, int reps, int precond, double* out8);
 std::string xr_refusal(System& S, int method, int precond, int op);
 void xr_info(System& S, double* out4);
 void xr_mg_info(System& S, double* out4);
@@ -411,7 +417,7 @@ int lsq_solve(lsq_handle* h, const double* b, double* x_inout, const lsq_opts* o
         if (o->method != 0 && o->method != 1) return fail(S, "lsq_solve: method must be 0 (LSQR) or 1 (CGNR)");
         if (o->precond < 0 || o->precond > 5) return fail(S, "lsq_solve: precond must be 0 .. 5");
         if (o->precond == 5 && S.dist) return fail(S, "lsq_solve: precond 5 (band factor) is single-GPU");
-        if (S.bias.nb || S.bias.ng) {
+        if (S.bias.nb || S.bias.ng || S.sgrid.ng) {
             const std::string why = lsq::bias_refusal(S, o->method, o->precond);
             if (!why.empty()) return fail(S, "lsq_solve: " + why);
         }
@@ -452,7 +458,7 @@ int lsq_iterate(lsq_handle* h, const double* b, int64_t iters, const lsq_opts* o
         lsq_opts d;
         lsq_default_opts(&d);
         if (!o) o = &d;
-        if (S.bias.nb || S.bias.ng) {
+        if (S.bias.nb || S.bias.ng || S.sgrid.ng) {
             const std::string why = lsq::bias_refusal(S, o->method, o->precond);
             if (!why.empty()) return fail(S, "lsq_iterate: " + why);
         }
@@ -482,7 +488,7 @@ int lsq_cg_available(lsq_handle* h, int32_t precond) {
             S.err = "CGNR runs with precond 1 (Jacobi), 3 (block-Jacobi) or 4 (multigrid)";
             return 0;
         }
-        if (S.bias.nb || S.bias.ng) {   // biases or slopes set: only the matrix-free CGNR operator carries them
+        if (S.bias.nb || S.bias.ng || S.sgrid.ng) {   // biases, slopes or sensor grids set: only the matrix-free CGNR operator carries them
             const std::string why = lsq::bias_refusal(S, 1, precond);
             if (!why.empty()) {
                 S.err = why;
@@ -611,6 +617,40 @@ int lsq_profile_data_slope(lsq_handle* h, int32_t reps, int32_t precond, double*
         if (!out8) return fail(S, "lsq_profile_data_slope: null output");
         lsq::graph_cache_drop(&S);
         lsq::cg_profile_slope(S, reps > 0 ? reps : 10, precond, out8);
+        return 0;
+    });
+}
+
+int lsq_set_sensor_grids(lsq_handle* h, int64_t npts, const int32_t* grid, const int32_t* node, const double* wt,
+                         int32_t ng, const int64_t* n_nodes, const int64_t* k_ptr, const int32_t* k_row,
+                         const int32_t* k_col, const double* k_val) {
+    return guarded(h, [&](lsq::System& S) {
+        if (!S.G.rp.p) return fail(S, "lsq_set_sensor_grids: no matrix");
+        if (ng < 0 || npts < 0) return fail(S, "lsq_set_sensor_grids: bad sizes");
+        if (ng == 0 || !grid || !node || !wt || !n_nodes) {
+            lsq::sgrid_clear(S);
+            return 0;
+        }
+        if (k_ptr && k_ptr[ng] > 0 && (!k_row || !k_col || !k_val)) return fail(S, "lsq_set_sensor_grids: K's arrays are null");
+        lsq::sgrid_set(S, npts, grid, node, wt, ng, n_nodes, k_ptr, k_row, k_col, k_val);
+        return 0;
+    });
+}
+
+int lsq_get_sensor_grids(lsq_handle* h, double* a) {
+    return guarded(h, [&](lsq::System& S) {
+        if (!a) return fail(S, "lsq_get_sensor_grids: null output");
+        lsq::sgrid_get(S, a);
+        return 0;
+    });
+}
+
+int lsq_profile_sensor_grids(lsq_handle* h, int32_t reps, int32_t precond, double* out8) {
+    return guarded(h, [&](lsq::System& S) {
+        if (!S.G.rp.p) return fail(S, "lsq_profile_sensor_grids: no matrix");
+        if (!out8) return fail(S, "lsq_profile_sensor_grids: null output");
+        lsq::graph_cache_drop(&S);
+        lsq::cg_profile_sgrid(S, reps > 0 ? reps : 10, precond, out8);
         return 0;
     });
 }

@@ -758,6 +758,7 @@ void finish_formation(System& S) {
     S.blk_user = false;
     S.blk_valid = false;
     S.bias = BiasData{};   // data biases index the previous formation's sorted points
+    S.sgrid = SgridData{}; // and so do the sensor grids' transpose and grid points
     HIP_CHECK(hipStreamSynchronize(st));
 }
 

@@ -2100,6 +2100,7 @@ void cg_launch_precond(System& S, const CgGrids& g, int precond) {
 bool cg_use_dmf(const System& S) { return S.cgh.colmode && S.dmf.ok; }
 
 #include "bias.inc"
+#include "sgrid.inc"
 #include "xrows.inc"
 
 // the data rows' row scales in the matrix-free point order (per solve)
@@ -2109,25 +2110,26 @@ void cg_dmf_prepare(System& S) {
                        S.rs.p, reinterpret_cast<double4*>(S.dmf_pt.p));
     KERNEL_CHECK();
     if (bias_active(S)) bias_prepare(S);
+    if (sgrid_active(S)) sgrid_prepare(S);
 }
 
 // the data rows' partials of pᵀNp: Σt² per workgroup, then (biases set) −Σ_j s_j²/D_j, then (extra
 // rows set) their Σt_x² per workgroup
 int cg_nt(const System& S, const CgGrids& g) {
-    return S.cgh.colmode ? g.gD + (bias_active(S) ? S.bias.nbk : 0) + (xr_active(S) ? S.xr.nbk : 0) : 0;
+    return S.cgh.colmode ? g.gD + elim_nbk(S) + (xr_active(S) ? S.xr.nbk : 0) : 0;
 }
 
 // extra rows set: t_x = W_x X p and q += Xᵀ W_x t_x, after q = N_s p (and its x-edge correction) and
 // before the node gather whose workgroup 0 sums the partials (xrows.inc)
 void cg_launch_xr(System& S, const CgGrids& g, const double* pnew) {
     if (!xr_active(S)) return;
-    xr_launch_fwd(S, S.cst.p, nullptr, pnew, 1.0, S.cg_part_t.p + g.gD + (bias_active(S) ? S.bias.nbk : 0));
+    xr_launch_fwd(S, S.cst.p, nullptr, pnew, 1.0, S.cg_part_t.p + g.gD + elim_nbk(S));
     xr_launch_atq(S, S.cst.p, S.cg_q.p);
 }
 
-// biases set: td ← W(I − Q)W A_d p between Ad·p and q += Adᵀ td (bias.inc)
+// biases or sensor grids set: td ← W(I − Q)W A_d p between Ad·p and q += Adᵀ td (bias.inc, sgrid.inc)
 void cg_launch_bias(System& S, const CgGrids& g) {
-    if (bias_active(S)) bias_launch_step(S, S.cst.p, S.cg_t.p, S.cg_part_t.p + g.gD);
+    if (elim_nbk(S)) elim_launch_step(S, S.cst.p, S.cg_t.p, S.cg_part_t.p + g.gD);
 }
 
 void cg_launch_data(System& S, const CgGrids& g, const double* pold, const double* pnew) {
@@ -2318,8 +2320,8 @@ void cg_init(System& S, const double* h_b, const double* h_x0, const lsq_opts& o
                            reinterpret_cast<const double4*>(S.dmf_pt.p), dbp, S.cg_t.p, S.part_u.p);
         KERNEL_CHECK();
         // biases set: td ← W(I − Q)W b and ‖r0‖² = bᵀW(I − Q)W b, the reduced problem's
-        const int nbk = bias_active(S) ? S.bias.nbk : 0;
-        if (nbk) bias_launch_step(S, S.cst.p, S.cg_t.p, S.part_u.p + gi);
+        const int nbk = elim_nbk(S);
+        if (nbk) elim_launch_step(S, S.cst.p, S.cg_t.p, S.part_u.p + gi);
         // extra rows: s0 += Xᵀ W_x² b_x, ‖r0‖² = ‖b‖² += ‖W_x b_x‖²
         const int nxk = xr_active(S) ? S.xr.nbk : 0;
         if (nxk) {
@@ -2339,21 +2341,23 @@ void cg_init(System& S, const double* h_b, const double* h_x0, const lsq_opts& o
         hipLaunchKernelGGL(k_mf_spmtv_for(S), dim3(lg.gM), dim3(BLOCK), 0, st, S.st.p, S.ATd.rp.p, S.ATd.ci.p,
                            S.ATd.val.p, S.mfd.p, S.u.p, S.rs.p, S.csf.p, S.cg_q.p, S.cg_s.p, S.zv.p, S.part_v.p, 1);
         KERNEL_CHECK();
-        const int nbk = bias_active(S) ? S.bias.nbk : 0;
+        const int nbk = elim_nbk(S);
         if (nbk) {
             // the reduced problem's u_d = (I − Q) W (b − A_d x0): with e = W²(b − A_d x0) per sorted point
             // and s_j = Σ_{i∈j} e_i, s0 −= A_dᵀ(W² s/D), ‖r0‖² −= Σ s_j²/D_j; the same on W b for ‖b‖
-            const BiasData& B = S.bias;
-            const int nu = lg.gD + lg.gS, ge = grid_for(B.npts);
-            hipLaunchKernelGGL(k_bias_resid, dim3(ge), dim3(BLOCK), 0, st, B.npts, S.dmf_perm.p, B.w2.p, dbp, nullptr,
+            // (sensor grids: the same with y = M⁻¹ Bᵀ e in place of s / D)
+            const int64_t enp = elim_npts(S);
+            const double* ew2 = elim_w2(S);
+            const int nu = lg.gD + lg.gS, ge = grid_for(enp);
+            hipLaunchKernelGGL(k_bias_resid, dim3(ge), dim3(BLOCK), 0, st, enp, S.dmf_perm.p, ew2, dbp, nullptr,
                                S.cg_t.p);
-            bias_launch_reduce(S, nullptr, S.cg_t.p, S.part_b.p + nu);
+            elim_launch_norm(S, nullptr, S.cg_t.p, S.part_b.p + nu);
             hipLaunchKernelGGL(k_cg_dmf_ad, dim3(g.gD), dim3(BLOCK), 0, st, S.cst.p, S.dmf,
                                reinterpret_cast<const double4*>(S.dmf_pt.p), S.cg_x.p, S.cg_t.p, S.cg_part_t.p);
-            hipLaunchKernelGGL(k_bias_resid, dim3(ge), dim3(BLOCK), 0, st, B.npts, S.dmf_perm.p, B.w2.p, dbp, S.cg_t.p,
+            hipLaunchKernelGGL(k_bias_resid, dim3(ge), dim3(BLOCK), 0, st, enp, S.dmf_perm.p, ew2, dbp, S.cg_t.p,
                                S.cg_t.p);
-            bias_launch_reduce(S, nullptr, S.cg_t.p, S.part_u.p + nu);
-            bias_launch_apply(S, nullptr, S.cg_t.p, 1);
+            elim_launch_reduce(S, nullptr, S.cg_t.p, S.part_u.p + nu);
+            elim_launch_apply(S, nullptr, S.cg_t.p, 1, S.part_u.p + nu);
             cg_launch_dmf_atq(S, S.cst.p, S.cg_t.p, S.cg_s.p);
             KERNEL_CHECK();
         }
@@ -2429,6 +2433,7 @@ void cg_kernel_bytes(const System& S, int precond, double out[3]) {
         const double ncell = (double)(S.dmf.S0 - 1) * (double)(S.dmf.S1 - 1);
         out[0] = 40.0 * md + 8.0 * nd + 4.0 * ncell + 40.0 * md + 16.0 * nd;
         if (bias_active(S)) out[0] += bias_step_bytes(S);
+        if (sgrid_active(S)) out[0] += sgrid_step_bytes(S);
         out[1] = 32.0 * nf;
     } else if (S.cgh.colmode) {
         // data = Ad·p (12 B/entry, p gathers, t) + ATd·t (entries, row pointers, t gathers, q RMW)
@@ -2470,6 +2475,7 @@ void cg_fill_stats(const CgState& h, lsq_stats* s) {
 }  // namespace
 
 void bias_values(System& S, const double* dbp);
+void sgrid_values(System& S, const double* dbp);
 
 bool cg_available(System& S, int precond) {
     if (precond != 1 && precond != 3 && precond != 4) return false;
@@ -2509,6 +2515,7 @@ int cg_solve(System& S, const double* h_b, double* h_x, const lsq_opts& o, lsq_s
     dx.download(h_x, n, S.stream);
     HIP_CHECK(hipStreamSynchronize(S.stream));
     if (S.bias.nb || S.bias.ng) bias_values(S, S.rhs.p);   // the biases and slopes that belong to this x
+    if (S.sgrid.ng) sgrid_values(S, S.rhs.p);              // the sensor grids that belong to this x
     float ms = 0.f;
     HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
     (void)hipEventDestroy(e0);
@@ -2680,7 +2687,7 @@ void cg_profile_xr(System& S, int reps, int precond, double* out) {
         HIP_CHECK(hipEventRecord(e[0], S.stream));
         cg_launch_data(S, g, pold, pnew);
         HIP_CHECK(hipEventRecord(e[1], S.stream));
-        xr_launch_fwd(S, S.cst.p, nullptr, pnew, 1.0, S.cg_part_t.p + g.gD + (bias_active(S) ? S.bias.nbk : 0));
+        xr_launch_fwd(S, S.cst.p, nullptr, pnew, 1.0, S.cg_part_t.p + g.gD + elim_nbk(S));
         HIP_CHECK(hipEventRecord(e[2], S.stream));
         xr_launch_atq(S, S.cst.p, S.cg_q.p);
         HIP_CHECK(hipEventRecord(e[3], S.stream));
@@ -2755,6 +2762,55 @@ void cg_profile_slope(System& S, int reps, int precond, double* out) {
     for (auto& e : ev) (void)hipEventDestroy(e);
     for (int k = 0; k < 4; ++k) out[k] = t[k] / reps;
     slope_kernel_bytes(S, out + 4);
+}
+
+// The sensor grids' elimination inside real iterations of a live lsq_iterate state (no stop), events
+// between the launches as in cg_profile_slope: out8 = {ms of s = Bᵀ td, of z = R⁻ᵀ s, of y = R⁻¹ z, of
+// the apply pass, and their algorithmic bytes (sgrid_kernel_bytes)}, means over reps iterations.
+void cg_profile_sgrid(System& S, int reps, int precond, double* out) {
+    if (!(S.cg_ready && S.cg_mode == precond))
+        throw std::invalid_argument("lsq_profile_sensor_grids: needs the live state of lsq_iterate with this precond");
+    if (!sgrid_active(S)) throw std::invalid_argument("lsq_profile_sensor_grids: no sensor grids in the CGNR operator");
+    const CgGrids g = cg_grids(S, precond);
+    std::vector<hipEvent_t> ev(5 * reps);
+    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+    for (int r = 0; r < reps; ++r) {
+        const int par = S.cg_parity;
+        const double* pold = cg_pold(S, par);
+        double* pnew = cg_pnew(S, par);
+        hipEvent_t* e = ev.data() + 5 * r;
+        cg_launch_normal(S, g, pold, pnew);
+        hipLaunchKernelGGL(k_cg_dmf_ad, dim3(g.gD), dim3(BLOCK), 0, S.stream, S.cst.p, S.dmf,
+                           reinterpret_cast<const double4*>(S.dmf_pt.p), pnew, S.cg_t.p, S.cg_part_t.p);
+        HIP_CHECK(hipEventRecord(e[0], S.stream));
+        sgrid_launch_btd(S, S.cst.p, S.cg_t.p);
+        HIP_CHECK(hipEventRecord(e[1], S.stream));
+        sgrid_launch_trsv_t(S, S.cst.p);
+        HIP_CHECK(hipEventRecord(e[2], S.stream));
+        sgrid_launch_trsv(S, S.cst.p);
+        HIP_CHECK(hipEventRecord(e[3], S.stream));
+        sgrid_launch_apply(S, S.cst.p, S.cg_t.p, 0, S.cg_part_t.p + g.gD);
+        HIP_CHECK(hipEventRecord(e[4], S.stream));
+        cg_launch_xr(S, g, pnew);
+        cg_launch_atdq(S);
+        cg_launch_alpha(S, g);
+        cg_launch_precond(S, g, precond);
+        hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(BLOCK), 0, S.stream, S.cst.p, S.cg_part_r.p, g.gB, 0, nullptr);
+        S.cg_parity = (S.cg_parity + 1) % CG_XK;
+    }
+    HIP_CHECK(hipStreamSynchronize(S.stream));
+    double t[4] = {0, 0, 0, 0};
+    for (int r = 0; r < reps; ++r) {
+        hipEvent_t* e = ev.data() + 5 * r;
+        for (int k = 0; k < 4; ++k) {
+            float a = 0.f;
+            HIP_CHECK(hipEventElapsedTime(&a, e[k], e[k + 1]));
+            t[k] += a;
+        }
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+    for (int k = 0; k < 4; ++k) out[k] = t[k] / reps;
+    sgrid_kernel_bytes(S, out + 4);
 }
 
 // The lumping pass of the multigrid set-up in place (lsq_profile_extra_rows_lumping): reps times the
@@ -2988,6 +3044,7 @@ void bias_build(System& S, int64_t npts, const int32_t* h_id, int64_t nb, const 
 // id: the data rows' bias IDs in the caller's row order; c: 1 / E_bias per ID.  Clears the slopes.
 void bias_set(System& S, int64_t npts, const int32_t* h_id, int64_t nb, const double* h_c) {
     if (!S.mf || S.dist) throw std::invalid_argument("lsq_set_data_bias: needs a single-GPU structured system (lsq_set_matrix_stencil)");
+    if (S.sgrid.ng) throw std::invalid_argument("lsq_set_data_bias: sensor grids are set (lsq_set_sensor_grids); clear them first");
     if (npts != S.mfh.npts) throw std::invalid_argument("lsq_set_data_bias: npts differs from the system's data rows");
     if (nb >= (int64_t)INT32_MAX) throw std::invalid_argument("lsq_set_data_bias: too many bias IDs");
     if (!S.dmf.ok || S.dmf.npts != npts)
@@ -3026,6 +3083,7 @@ void slope_clear(System& S) {
 // c: two constraint weights per group
 void slope_set(System& S, int64_t npts, const int32_t* h_grp, const double* h_u, int64_t ng, const double* h_c) {
     if (!S.mf || S.dist) throw std::invalid_argument("lsq_set_data_slope: needs a single-GPU structured system (lsq_set_matrix_stencil)");
+    if (S.sgrid.ng) throw std::invalid_argument("lsq_set_data_slope: sensor grids are set (lsq_set_sensor_grids); clear them first");
     if (npts != S.mfh.npts) throw std::invalid_argument("lsq_set_data_slope: npts differs from the system's data rows");
     if (ng >= (int64_t)INT32_MAX - 1) throw std::invalid_argument("lsq_set_data_slope: too many slope groups");
     if (!S.dmf.ok || S.dmf.npts != npts)
@@ -3098,10 +3156,195 @@ void slope_get(System& S, double* h_g) {
     HIP_CHECK(hipStreamSynchronize(S.stream));
 }
 
-// why a solve with biases or slopes set cannot run (empty: it can)
+// ---- sensor bias grids (sgrid.inc): set, clear, read back ----------------------------------------
+void sgrid_clear(System& S) {
+    if (!S.sgrid.ng) return;
+    graph_cache_drop(&S);   // captured iterations hold the step's launches
+    S.sgrid = SgridData{};
+    S.cg_ready = false;
+}
+
+// grid: the data rows' grids (−1: none) in the caller's row order; node, wt: four local nodes and
+// weights per row; n_nodes per grid; K_s as triplets k_ptr[s] … k_ptr[s + 1] with local rows and columns.
+// Every check runs before anything of the handle changes.
+void sgrid_set(System& S, int64_t npts, const int32_t* h_grid, const int32_t* h_node, const double* h_wt, int64_t ng,
+               const int64_t* h_nn, const int64_t* k_ptr, const int32_t* k_row, const int32_t* k_col,
+               const double* k_val) {
+    if (!S.mf || S.dist) throw std::invalid_argument("lsq_set_sensor_grids: needs a single-GPU structured system (lsq_set_matrix_stencil)");
+    if (S.bias.nb || S.bias.ng) throw std::invalid_argument("lsq_set_sensor_grids: data biases or slopes are set; the joint block is not one matrix per grid");
+    if (npts != S.mfh.npts) throw std::invalid_argument("lsq_set_sensor_grids: npts differs from the system's data rows");
+    if (!S.dmf.ok || S.dmf.npts != npts)
+        throw std::invalid_argument("lsq_set_sensor_grids: needs matrix-free data rows (interpolation grids on one (y, x) lattice)");
+    std::vector<int64_t> nn(h_nn, h_nn + ng), npad(ng), poff(ng + 1, 0), moff(ng + 1, 0);
+    for (int64_t g = 0; g < ng; ++g) {
+        if (nn[g] < 1 || nn[g] > SG_MAX_NODES)
+            throw std::invalid_argument("lsq_set_sensor_grids: grid " + std::to_string(g) + " has " + std::to_string(nn[g]) +
+                                        " nodes; a grid holds 1 … " + std::to_string(SG_MAX_NODES) + " (the size cap)");
+        npad[g] = (nn[g] + 63) / 64 * 64;
+        poff[g + 1] = poff[g] + npad[g];
+        moff[g + 1] = moff[g] + npad[g] * npad[g];
+        if (moff[g + 1] * (int64_t)sizeof(double) > SG_MAX_FACTOR_BYTES)
+            throw std::invalid_argument("lsq_set_sensor_grids: the grids' inverse factors exceed the size cap of " +
+                                        std::to_string(SG_MAX_FACTOR_BYTES) + " bytes");
+    }
+    const int64_t ntp = poff[ng];
+    if (k_ptr && k_ptr[0] != 0) throw std::invalid_argument("lsq_set_sensor_grids: k_ptr must start at 0");
+    std::vector<std::pair<int64_t, double>> kent;   // (position, value), input order
+    for (int64_t g = 0; g < ng && k_ptr; ++g) {
+        if (k_ptr[g + 1] < k_ptr[g]) throw std::invalid_argument("lsq_set_sensor_grids: k_ptr must not decrease");
+        for (int64_t t = k_ptr[g]; t < k_ptr[g + 1]; ++t) {
+            if (k_row[t] < 0 || k_row[t] >= nn[g] || k_col[t] < 0 || k_col[t] >= nn[g])
+                throw std::invalid_argument("lsq_set_sensor_grids: an entry of K lies outside its grid's nodes");
+            if (!std::isfinite(k_val[t])) throw std::invalid_argument("lsq_set_sensor_grids: a value of K is not finite");
+            kent.emplace_back(moff[g] + (int64_t)k_row[t] * npad[g] + k_col[t], k_val[t]);
+        }
+    }
+    for (int64_t i = 0; i < npts; ++i) {
+        const int32_t g = h_grid[i];
+        if (g < -1 || g >= ng) throw std::invalid_argument("lsq_set_sensor_grids: a grid lies outside {-1} and [0, ng)");
+        if (g < 0) continue;
+        for (int q = 0; q < 4; ++q) {
+            if (h_node[4 * i + q] < 0 || h_node[4 * i + q] >= nn[g])
+                throw std::invalid_argument("lsq_set_sensor_grids: a node lies outside its grid");
+            if (!std::isfinite(h_wt[4 * i + q])) throw std::invalid_argument("lsq_set_sensor_grids: a weight is not finite");
+        }
+    }
+    std::vector<int32_t> perm(std::max<int64_t>(npts, 1));
+    S.dmf_perm.download(perm.data(), npts, S.stream);
+    HIP_CHECK(hipStreamSynchronize(S.stream));
+    // the rows that lie in a grid, in sorted point order; the transpose by padded node in that order
+    std::vector<int32_t> gp_pt, gp_node;
+    std::vector<double> gp_wt;
+    std::vector<int64_t> tr_ptr(ntp + 1, 0);
+    for (int64_t i = 0; i < npts; ++i) {
+        const int64_t r = perm[i];
+        const int32_t g = h_grid[r];
+        if (g < 0) continue;
+        gp_pt.push_back((int32_t)i);
+        for (int q = 0; q < 4; ++q) {
+            const int32_t k = (int32_t)(poff[g] + h_node[4 * r + q]);
+            gp_node.push_back(k);
+            gp_wt.push_back(h_wt[4 * r + q]);
+            if (h_wt[4 * r + q] != 0.0) ++tr_ptr[k + 1];
+        }
+    }
+    const int64_t ngp = (int64_t)gp_pt.size();
+    for (int64_t k = 0; k < ntp; ++k) tr_ptr[k + 1] += tr_ptr[k];
+    const int64_t nent = tr_ptr[ntp];
+    if (nent >= (int64_t)INT32_MAX) throw std::invalid_argument("lsq_set_sensor_grids: too many entries");
+    std::vector<int32_t> tr_pt(std::max<int64_t>(nent, 1)), tr_gp(std::max<int64_t>(nent, 1)), nbr(std::max<int64_t>(ntp, 1) * SG_NBR, -1);
+    std::vector<uint32_t> tr_slot(std::max<int64_t>(nent, 1));
+    std::vector<double> tr_w(std::max<int64_t>(nent, 1));
+    std::vector<int64_t> fill(tr_ptr.begin(), tr_ptr.end() - 1);
+    for (int64_t j = 0; j < ngp; ++j)
+        for (int q0 = 0; q0 < 4; ++q0) {
+            if (gp_wt[4 * j + q0] == 0.0) continue;
+            const int32_t k = gp_node[4 * j + q0];
+            const int64_t e = fill[k]++;
+            tr_pt[e] = gp_pt[j];
+            tr_gp[e] = (int32_t)j;
+            tr_w[e] = gp_wt[4 * j + q0];
+            uint32_t sl = 0;
+            for (int q = 0; q < 4; ++q) {
+                uint32_t slot = 255;
+                if (gp_wt[4 * j + q] != 0.0) {
+                    int32_t* nb = nbr.data() + (int64_t)k * SG_NBR;
+                    int c = 0;
+                    while (c < SG_NBR && nb[c] >= 0 && nb[c] != gp_node[4 * j + q]) ++c;
+                    if (c == SG_NBR)
+                        throw std::invalid_argument("lsq_set_sensor_grids: a node shares rows with more than 9 nodes "
+                                                    "(the rows must be cells of a lattice)");
+                    nb[c] = gp_node[4 * j + q];
+                    slot = (uint32_t)c;
+                }
+                sl |= slot << (8 * q);
+            }
+            tr_slot[e] = sl;
+        }
+    // K: duplicates summed in input order
+    std::stable_sort(kent.begin(), kent.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+    std::vector<int64_t> k_pos;
+    std::vector<double> k_sum;
+    for (const auto& kv : kent) {
+        if (!k_pos.empty() && k_pos.back() == kv.first)
+            k_sum.back() += kv.second;
+        else {
+            k_pos.push_back(kv.first);
+            k_sum.push_back(kv.second);
+        }
+    }
+    std::vector<int32_t> node_grid(std::max<int64_t>(ntp, 1), 0), tile_grid, tile_jb;
+    for (int64_t g = 0; g < ng; ++g) {
+        for (int64_t k = poff[g]; k < poff[g + 1]; ++k) node_grid[k] = (int32_t)g;
+        for (int64_t jb = 0; jb < npad[g] / 64; ++jb) {
+            tile_grid.push_back((int32_t)g);
+            tile_jb.push_back((int32_t)jb);
+        }
+    }
+    // device memory first: a failed allocation leaves the handle as it was
+    SgridData N;
+    N.ng = ng; N.npts = npts; N.ntp = ntp; N.ngp = ngp; N.nent = nent;
+    N.ntile = (int64_t)tile_grid.size(); N.nk = (int64_t)k_pos.size(); N.fsum = moff[ng];
+    for (int64_t g = 0; g < ng; ++g) N.ntot += nn[g];
+    N.nbk = grid_for(ntp, BLOCK, BIAS_NPART);
+    N.h_nn = nn; N.h_npad = npad; N.h_poff = poff; N.h_moff = moff;
+    auto up = [&](auto& d, const auto& h) {
+        d.alloc(std::max<int64_t>((int64_t)h.size(), 1));
+        d.upload(h.data(), (int64_t)h.size(), S.stream);
+    };
+    gp_pt.resize(std::max<int64_t>(ngp, 1));
+    gp_node.resize(4 * std::max<int64_t>(ngp, 1));
+    gp_wt.resize(4 * std::max<int64_t>(ngp, 1));
+    up(N.tr_ptr, tr_ptr); up(N.tr_pt, tr_pt); up(N.tr_gp, tr_gp); up(N.tr_slot, tr_slot); up(N.tr_w, tr_w);
+    up(N.gp_pt, gp_pt); up(N.gp_node, gp_node); up(N.gp_wt, gp_wt); up(N.nbr, nbr); up(N.node_grid, node_grid);
+    up(N.poff, poff); up(N.moff, moff); up(N.npad, npad); up(N.nn, nn); up(N.tile_grid, tile_grid); up(N.tile_jb, tile_jb);
+    up(N.k_pos, k_pos); up(N.k_val, k_sum);
+    N.w2.alloc(std::max<int64_t>(npts, 1));
+    N.M.alloc(N.fsum); N.Ri.alloc(N.fsum);
+    N.d0.alloc(ntp); N.err.alloc(ng);
+    N.s.alloc(ntp); N.z.alloc(ntp); N.y.alloc(ntp);
+    N.aval.assign(N.ntot, 0.0);
+    HIP_CHECK(hipStreamSynchronize(S.stream));   // the uploads read host vectors of this scope
+    N.on = npts > 0;
+    graph_cache_drop(&S);   // captured iterations hold no elimination step yet
+    S.sgrid = std::move(N);
+    S.cg_ready = false;
+}
+
+// the grids of the x in S.cg_x (full space) for the right-hand side dbp: a = M⁻¹ Bᵀ W² (d − A_d x)
+void sgrid_values(System& S, const double* dbp) {
+    SgridData& G = S.sgrid;
+    std::fill(G.aval.begin(), G.aval.end(), 0.0);
+    if (sgrid_active(S)) {
+        const CgGrids g = cg_grids(S, 1);
+        DBuf<CgState> st(1);
+        st.zero(S.stream);
+        hipLaunchKernelGGL(k_cg_dmf_ad, dim3(g.gD), dim3(BLOCK), 0, S.stream, st.p, S.dmf,
+                           reinterpret_cast<const double4*>(S.dmf_pt.p), S.cg_x.p, S.cg_t.p, S.cg_part_t.p);
+        hipLaunchKernelGGL(k_bias_resid, dim3(grid_for(G.npts)), dim3(BLOCK), 0, S.stream, G.npts, S.dmf_perm.p, G.w2.p,
+                           dbp, S.cg_t.p, S.cg_t.p);
+        sgrid_launch_reduce(S, nullptr, S.cg_t.p);
+        KERNEL_CHECK();
+        std::vector<double> y(G.ntp);
+        G.y.download(y.data(), G.ntp, S.stream);
+        HIP_CHECK(hipStreamSynchronize(S.stream));
+        int64_t o = 0;
+        for (int64_t s = 0; s < G.ng; ++s)
+            for (int64_t k = 0; k < G.h_nn[s]; ++k) G.aval[o++] = y[G.h_poff[s] + k];
+    }
+    G.solved = true;
+}
+
+void sgrid_get(System& S, double* h_a) {
+    if (!S.sgrid.ng) throw std::invalid_argument("lsq_get_sensor_grids: no sensor grids set");
+    if (!S.sgrid.solved) throw std::invalid_argument("lsq_get_sensor_grids: no lsq_solve since the grids were set");
+    std::copy(S.sgrid.aval.begin(), S.sgrid.aval.end(), h_a);
+}
+
+// why a solve with biases, slopes or sensor grids set cannot run (empty: it can)
 std::string bias_refusal(System& S, int method, int precond) {
-    if (!S.bias.nb && !S.bias.ng) return "";
-    const std::string what = S.bias.nb ? "data biases" : "data slopes";
+    if (!S.bias.nb && !S.bias.ng && !S.sgrid.ng) return "";
+    const std::string what = S.sgrid.ng ? "sensor grids" : (S.bias.nb ? "data biases" : "data slopes");
     if (S.dist) return what + " run on single-GPU handles only";
     if (method != 1) return what + " need CGNR (method 1)";
     if (precond != 1 && precond != 3 && precond != 4) return what + " run with precond 1, 3 or 4";

@@ -1,0 +1,331 @@
+// sgrid.inc — sensor bias grids eliminated from the CGNR normal equations (lsq_set_sensor_grids).
+// Included by lsqr_cg.inc inside its anonymous namespace, behind bias.inc.
+//
+// The data rows of grid s gain the unknowns a_s (the grid's node values) with the bilinear weights
+// β_i (≤ 4 per row), and the grid is held by the constraint rows C_s a_s = 0.  For fixed x the optimal
+// a = M⁻¹ Bᵀ W² (d − A_d x) with M = BᵀW²B + K, K_s = C_sᵀC_s, and substituting it back leaves the
+// normal operator N − A_dᵀ W² B M⁻¹ Bᵀ W² A_d.  A row lies in one grid and C_s touches its own nodes
+// only: M is one dense SPD block per grid.  On td_i = W_i² (A_d p)_i, which the CG step holds between
+// k_cg_dmf_ad and the node gather, the elimination is
+//   s = Bᵀ td,   y_s = R_s⁻¹ R_s⁻ᵀ s_s,   td_i −= W_i² Σ_k β_ik y_k,   pᵀNp −= Σ_k s_k y_k
+// with M_s = R_sᵀR_s: four launches, whatever the number of grids (k_sg_btd, k_sg_trsv_t, k_sg_trsv,
+// k_sg_apply).  M_s is assembled and factored once per solve (the weights and the mask change with
+// every outer iteration): k_sg_asm, k_sg_addk, dense_spd_factor per grid.
+//
+// Reproducibility (SgridData, system.hpp): the transpose by node lists its entries in point order; a
+// wave sums them lane-strided and with the fixed shuffle tree; the triangular products add in index
+// order.  No atomics: two runs agree bit for bit.
+
+// s_k = Σ_{e ∈ k} β_e src[pt_e]: a wave per padded node over its transpose entries
+__global__ __launch_bounds__(BLOCK) void k_sg_btd(const CgState* __restrict__ st, int64_t ntp,
+                                                  const int64_t* __restrict__ tr_ptr,
+                                                  const int32_t* __restrict__ tr_pt,
+                                                  const double* __restrict__ tr_w, const double* __restrict__ src,
+                                                  double* __restrict__ s) {
+    if (st && st->stop) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t nw = (int64_t)gridDim.x * (BLOCK / 64);
+    // whole waves leave the loop together: k is wave-uniform
+    for (int64_t k = (int64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6); k < ntp; k += nw) {
+        const int64_t lo = tr_ptr[k], hi = tr_ptr[k + 1];
+        double t = 0.0;
+        for (int64_t e = lo + lane; e < hi; e += 64) t += tr_w[e] * src[tr_pt[e]];
+        t = wave_sum(t);
+        if (lane == 0) s[k] = t;
+    }
+}
+
+// z = R⁻ᵀ s per grid: z_j = Σ_{i ≤ j} Ri[i][j] s_i.  A workgroup per 64-column tile of a grid, lane =
+// column (coalesced along the rows of Ri); the four waves take the four quarters of the rows
+// [0, j0 + 64) (Ri is zero below its diagonal) and their sums are added in wave order.
+__global__ __launch_bounds__(BLOCK) void k_sg_trsv_t(const CgState* __restrict__ st, int64_t ntile,
+                                                     const int32_t* __restrict__ tile_grid,
+                                                     const int32_t* __restrict__ tile_jb,
+                                                     const int64_t* __restrict__ poff,
+                                                     const int64_t* __restrict__ moff,
+                                                     const int64_t* __restrict__ npad, const double* __restrict__ Ri,
+                                                     const double* __restrict__ s, double* __restrict__ z) {
+    if (st && st->stop) return;
+    __shared__ double red[BLOCK];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int64_t t = blockIdx.x; t < ntile; t += gridDim.x) {   // block-uniform: the barriers see every thread
+        const int32_t g = tile_grid[t];
+        const int64_t np = npad[g], j0 = (int64_t)tile_jb[t] * 64;
+        const double* R = Ri + moff[g];
+        const double* sg = s + poff[g];
+        const int64_t q = (j0 + 64) / 4;   // a multiple of 16
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+        for (int64_t i = w * q; i < (w + 1) * q; i += 4) {
+            a0 += R[i * np + j0 + lane] * sg[i];
+            a1 += R[(i + 1) * np + j0 + lane] * sg[i + 1];
+            a2 += R[(i + 2) * np + j0 + lane] * sg[i + 2];
+            a3 += R[(i + 3) * np + j0 + lane] * sg[i + 3];
+        }
+        red[threadIdx.x] = (a0 + a1) + (a2 + a3);
+        __syncthreads();
+        if (w == 0) z[poff[g] + j0 + lane] = (red[lane] + red[64 + lane]) + (red[128 + lane] + red[192 + lane]);
+        __syncthreads();
+    }
+}
+
+// y = R⁻¹ z per grid: y_i = Σ_{j ≥ i} Ri[i][j] z_j, a wave per padded node (row), lanes along the row
+__global__ __launch_bounds__(BLOCK) void k_sg_trsv(const CgState* __restrict__ st, int64_t ntp,
+                                                   const int32_t* __restrict__ node_grid,
+                                                   const int64_t* __restrict__ poff,
+                                                   const int64_t* __restrict__ moff,
+                                                   const int64_t* __restrict__ npad, const double* __restrict__ Ri,
+                                                   const double* __restrict__ z, double* __restrict__ y) {
+    if (st && st->stop) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t nw = (int64_t)gridDim.x * (BLOCK / 64);
+    for (int64_t k = (int64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6); k < ntp; k += nw) {   // wave-uniform
+        const int32_t g = node_grid[k];
+        const int64_t np = npad[g], i = k - poff[g];
+        const double* R = Ri + moff[g] + i * np;
+        const double* zg = z + poff[g];
+        double t = 0.0;
+        for (int64_t j = i / 64 * 64 + lane; j < np; j += 64) t += R[j] * zg[j];   // zeros left of the diagonal
+        t = wave_sum(t);
+        if (lane == 0) y[k] = t;
+    }
+}
+
+// mode 0: td_i −= w_i² Σ_k β_ik y_k over the rows that lie in a grid; mode 1: td_i = −(that) (the rows
+// outside are zeroed by the caller).  part (nullable): the first npart workgroups also store their
+// share of −Σ_k s_k y_k (fixed strides over the padded nodes)
+__global__ __launch_bounds__(BLOCK) void k_sg_apply(const CgState* __restrict__ st, int64_t ngp,
+                                                    const int32_t* __restrict__ gp_pt,
+                                                    const int4* __restrict__ gp_node,
+                                                    const double4* __restrict__ gp_wt, const double* __restrict__ w2,
+                                                    const double* __restrict__ y, double* __restrict__ td, int mode,
+                                                    int64_t ntp, const double* __restrict__ s, double* part,
+                                                    int npart) {
+    if (st && st->stop) return;
+    for (int64_t j = (int64_t)blockIdx.x * BLOCK + threadIdx.x; j < ngp; j += (int64_t)gridDim.x * BLOCK) {
+        const int32_t i = gp_pt[j];
+        const int4 n = gp_node[j];
+        const double4 b = gp_wt[j];
+        const double d = w2[i] * (((b.x * y[n.x] + b.y * y[n.y]) + b.z * y[n.z]) + b.w * y[n.w]);
+        td[i] = mode ? -d : td[i] - d;
+    }
+    if (part && (int)blockIdx.x < npart) {   // block-uniform
+        double acc = 0.0;
+        for (int64_t k = (int64_t)blockIdx.x * BLOCK + threadIdx.x; k < ntp; k += (int64_t)npart * BLOCK)
+            acc -= s[k] * y[k];
+        store_partial(acc, part, blockIdx.x);
+    }
+}
+
+// per solve: row k of M = BᵀW²B.  A wave per padded node k walks k's transpose entries; an entry's
+// row adds w² β_k β_m to the column of each of its ≤ 4 nodes m, which are among the ≤ SG_NBR nodes
+// that share a row with k (tr_slot: their places in nbr).  Padding nodes: the identity.
+__global__ __launch_bounds__(BLOCK) void k_sg_asm(int64_t ntp, const int64_t* __restrict__ tr_ptr,
+                                                  const int32_t* __restrict__ tr_pt,
+                                                  const int32_t* __restrict__ tr_gp,
+                                                  const uint32_t* __restrict__ tr_slot,
+                                                  const double* __restrict__ tr_w, const double* __restrict__ gp_wt,
+                                                  const double* __restrict__ w2, const int32_t* __restrict__ nbr,
+                                                  const int32_t* __restrict__ node_grid,
+                                                  const int64_t* __restrict__ poff,
+                                                  const int64_t* __restrict__ moff,
+                                                  const int64_t* __restrict__ npad, const int64_t* __restrict__ nn,
+                                                  double* __restrict__ M) {
+    const int lane = threadIdx.x & 63;
+    const int64_t nw = (int64_t)gridDim.x * (BLOCK / 64);
+    for (int64_t k = (int64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6); k < ntp; k += nw) {   // wave-uniform
+        const int32_t g = node_grid[k];
+        const int64_t np = npad[g], p0 = poff[g], i = k - p0;
+        double* row = M + moff[g] + i * np;
+        if (i >= nn[g]) {
+            if (lane == 0) row[i] = 1.0;
+            continue;
+        }
+        double acc[SG_NBR];
+#pragma unroll
+        for (int c = 0; c < SG_NBR; ++c) acc[c] = 0.0;
+        for (int64_t e = tr_ptr[k] + lane; e < tr_ptr[k + 1]; e += 64) {
+            const double ww = w2[tr_pt[e]] * tr_w[e];
+            const uint32_t sl = tr_slot[e];
+            const double* b = gp_wt + 4 * (int64_t)tr_gp[e];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int slot = (int)((sl >> (8 * q)) & 255u);
+                const double v = ww * b[q];
+#pragma unroll
+                for (int c = 0; c < SG_NBR; ++c)
+                    if (slot == c) acc[c] += v;
+            }
+        }
+        double mine = 0.0;
+#pragma unroll
+        for (int c = 0; c < SG_NBR; ++c) {
+            const double t = wave_sum(acc[c]);
+            if (lane == c) mine = t;
+        }
+        if (lane < SG_NBR) {
+            const int32_t m = nbr[k * SG_NBR + lane];
+            if (m >= 0) row[m - p0] = mine;
+        }
+    }
+}
+
+// per solve: M += K (K's entries are distinct positions: plain read-modify-write)
+__global__ __launch_bounds__(BLOCK) void k_sg_addk(int64_t nk, const int64_t* __restrict__ k_pos,
+                                                   const double* __restrict__ k_val, double* __restrict__ M) {
+    for (int64_t t = (int64_t)blockIdx.x * BLOCK + threadIdx.x; t < nk; t += (int64_t)gridDim.x * BLOCK)
+        M[k_pos[t]] += k_val[t];
+}
+
+// mode 0 (before the factorisation): d0 = diag M.  mode 1 (after it): err[grid] = 1 where the pivot
+// R_kk² is not above SG_PIVOT_REL of M_kk — a grid whose matrix is singular to rounding (the
+// factorisation itself flags only pivots ≤ 0, and rounding may leave a tiny positive one)
+constexpr double SG_PIVOT_REL = 1e-12;
+__global__ __launch_bounds__(BLOCK) void k_sg_diag(int64_t ntp, const int32_t* __restrict__ node_grid,
+                                                   const int64_t* __restrict__ poff,
+                                                   const int64_t* __restrict__ moff,
+                                                   const int64_t* __restrict__ npad, const double* __restrict__ M,
+                                                   double* __restrict__ d0, int mode, int* __restrict__ err) {
+    for (int64_t k = (int64_t)blockIdx.x * BLOCK + threadIdx.x; k < ntp; k += (int64_t)gridDim.x * BLOCK) {
+        const int32_t g = node_grid[k];
+        const int64_t i = k - poff[g];
+        const double v = M[moff[g] + i * npad[g] + i];
+        if (mode == 0)
+            d0[k] = v;
+        else if (!(v * v > SG_PIVOT_REL * d0[k]))
+            err[g] = 1;   // every writer stores the same value
+    }
+}
+
+// the grids take part in this system's CGNR operator
+inline bool sgrid_active(const System& S) { return S.sgrid.on && !S.dist && cg_use_dmf(S); }
+
+// the three launches of y = M⁻¹ Bᵀ src, one by one (the profile places events between them)
+void sgrid_launch_btd(const System& S, const CgState* st, const double* src) {
+    const SgridData& G = S.sgrid;
+    hipLaunchKernelGGL(k_sg_btd, dim3(grid_for(G.ntp, BLOCK / 64)), dim3(BLOCK), 0, S.stream, st, G.ntp, G.tr_ptr.p,
+                       G.tr_pt.p, G.tr_w.p, src, G.s.p);
+}
+
+void sgrid_launch_trsv_t(const System& S, const CgState* st) {
+    const SgridData& G = S.sgrid;
+    hipLaunchKernelGGL(k_sg_trsv_t, dim3(grid_for(G.ntile, 1)), dim3(BLOCK), 0, S.stream, st, G.ntile, G.tile_grid.p,
+                       G.tile_jb.p, G.poff.p, G.moff.p, G.npad.p, G.Ri.p, G.s.p, G.z.p);
+}
+
+void sgrid_launch_trsv(const System& S, const CgState* st) {
+    const SgridData& G = S.sgrid;
+    hipLaunchKernelGGL(k_sg_trsv, dim3(grid_for(G.ntp, BLOCK / 64)), dim3(BLOCK), 0, S.stream, st, G.ntp,
+                       G.node_grid.p, G.poff.p, G.moff.p, G.npad.p, G.Ri.p, G.z.p, G.y.p);
+}
+
+// y = M⁻¹ Bᵀ src (src per sorted point); s and z stay for the partials of k_sg_apply
+void sgrid_launch_reduce(const System& S, const CgState* st, const double* src) {
+    sgrid_launch_btd(S, st, src);
+    sgrid_launch_trsv_t(S, st);
+    sgrid_launch_trsv(S, st);
+}
+
+// mode 0: td −= W² B y; mode 1: td = −W² B y (after sgrid_launch_reduce); part (nullable): G.nbk
+// partials of −Σ_k s_k y_k
+void sgrid_launch_apply(const System& S, const CgState* st, double* td, int mode, double* part) {
+    const SgridData& G = S.sgrid;
+    if (mode) HIP_CHECK(hipMemsetAsync(td, 0, sizeof(double) * (size_t)G.npts, S.stream));   // the rows outside every grid
+    const int grid = std::max(grid_for(G.ngp), G.nbk);
+    hipLaunchKernelGGL(k_sg_apply, dim3(grid), dim3(BLOCK), 0, S.stream, st, G.ngp, G.gp_pt.p,
+                       reinterpret_cast<const int4*>(G.gp_node.p), reinterpret_cast<const double4*>(G.gp_wt.p), G.w2.p,
+                       G.y.p, td, mode, G.ntp, G.s.p, part, G.nbk);
+}
+
+// per solve (beside k_dmf_rs): w² per sorted point, M_s = Σ w² β βᵀ + K_s and its factor for the
+// current weights / mask.  Throws (naming the grid) when some M_s is not positive definite.
+void sgrid_prepare(System& S) {
+    SgridData& G = S.sgrid;
+    hipStream_t st = S.stream;
+    hipLaunchKernelGGL(k_bias_w2, dim3(grid_for(G.npts)), dim3(BLOCK), 0, st, G.npts, S.dmf_perm.p, S.rs.p, G.w2.p);
+    G.M.zero(st);
+    G.err.zero(st);
+    hipLaunchKernelGGL(k_sg_asm, dim3(grid_for(G.ntp, BLOCK / 64)), dim3(BLOCK), 0, st, G.ntp, G.tr_ptr.p, G.tr_pt.p,
+                       G.tr_gp.p, G.tr_slot.p, G.tr_w.p, G.gp_wt.p, G.w2.p, G.nbr.p, G.node_grid.p, G.poff.p, G.moff.p,
+                       G.npad.p, G.nn.p, G.M.p);
+    if (G.nk) hipLaunchKernelGGL(k_sg_addk, dim3(grid_for(G.nk)), dim3(BLOCK), 0, st, G.nk, G.k_pos.p, G.k_val.p, G.M.p);
+    hipLaunchKernelGGL(k_sg_diag, dim3(grid_for(G.ntp)), dim3(BLOCK), 0, st, G.ntp, G.node_grid.p, G.poff.p, G.moff.p,
+                       G.npad.p, G.M.p, G.d0.p, 0, G.err.p);
+    KERNEL_CHECK();
+    for (int64_t g = 0; g < G.ng; ++g)
+        dense_spd_factor(G.M.p + G.h_moff[g], G.Ri.p + G.h_moff[g], G.h_npad[g], G.err.p + g, st);
+    hipLaunchKernelGGL(k_sg_diag, dim3(grid_for(G.ntp)), dim3(BLOCK), 0, st, G.ntp, G.node_grid.p, G.poff.p, G.moff.p,
+                       G.npad.p, G.M.p, G.d0.p, 1, G.err.p);
+    KERNEL_CHECK();
+    std::vector<int> herr(G.ng, 0);
+    G.err.download(herr.data(), G.ng, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+    for (int64_t g = 0; g < G.ng; ++g)
+        if (herr[g])
+            throw std::invalid_argument("sensor grid " + std::to_string(g) + ": BᵀW²B + K has a pivot that is not "
+                                        "positive (the kept data and the constraints do not determine the grid)");
+}
+
+// algorithmic bytes of the step's kernels, out = {s = Bᵀ td, z = R⁻ᵀ s, y = R⁻¹ z, apply}.  Bᵀ td: the
+// entries' point, weight and gathered td (20 B), the node pointers and s.  The two triangular products
+// each read the upper half of every R_s⁻¹ (with the diagonal tiles whole) and three vectors.  Apply: the
+// grid points' index, nodes, weights, w², td read and written (76 B), y gathered within the grid, and
+// s, y for the partials.
+void sgrid_kernel_bytes(const System& S, double out[4]) {
+    const SgridData& G = S.sgrid;
+    double tri = 0.0;
+    for (int64_t g = 0; g < G.ng; ++g) {
+        const double nb = (double)(G.h_npad[g] / 64);
+        tri += nb * (nb + 1.0) / 2.0 * 64.0 * 64.0 * 8.0;
+    }
+    out[0] = 20.0 * (double)G.nent + 16.0 * (double)G.ntp;
+    out[1] = tri + 16.0 * (double)G.ntp;
+    out[2] = tri + 20.0 * (double)G.ntp;
+    out[3] = 76.0 * (double)G.ngp + 24.0 * (double)G.ntp;
+}
+
+double sgrid_step_bytes(const System& S) {
+    double k[4];
+    sgrid_kernel_bytes(S, k);
+    return k[0] + k[1] + k[2] + k[3];
+}
+
+// ---- one interface over the two eliminations (biases / slopes, or sensor grids; never both) -----
+inline int elim_nbk(const System& S) { return bias_active(S) ? S.bias.nbk : (sgrid_active(S) ? S.sgrid.nbk : 0); }
+inline const double* elim_w2(const System& S) { return S.sgrid.on ? S.sgrid.w2.p : S.bias.w2.p; }
+inline int64_t elim_npts(const System& S) { return S.sgrid.on ? S.sgrid.npts : S.bias.npts; }
+
+// the eliminated unknowns for the sums of src; part (nullable) as in elim_launch_step.  With sensor
+// grids the partials are written by the apply pass: elim_launch_apply must follow with the same part.
+void elim_launch_reduce(const System& S, const CgState* st, const double* src, double* part) {
+    if (S.sgrid.on)
+        sgrid_launch_reduce(S, st, src);
+    else
+        bias_launch_reduce(S, st, src, part);
+}
+
+void elim_launch_apply(const System& S, const CgState* st, double* td, int mode, double* part) {
+    if (S.sgrid.on)
+        sgrid_launch_apply(S, st, td, mode, part);
+    else
+        bias_launch_apply(S, st, td, mode);
+}
+
+// the elimination step on td (W² A_d p per sorted point): td ← W (I − Q) W A_d p; part: elim_nbk
+// partials of what the elimination takes off pᵀNp
+void elim_launch_step(const System& S, const CgState* st, double* td, double* part) {
+    elim_launch_reduce(S, st, td, part);
+    elim_launch_apply(S, st, td, 0, part);
+}
+
+// the partials alone (the norm of W b in the general start): src is left as it is
+void elim_launch_norm(const System& S, const CgState* st, const double* src, double* part) {
+    if (S.sgrid.on) {
+        const SgridData& G = S.sgrid;
+        sgrid_launch_reduce(S, st, src);
+        hipLaunchKernelGGL(k_sg_apply, dim3(G.nbk), dim3(BLOCK), 0, S.stream, st, (int64_t)0, G.gp_pt.p,
+                           reinterpret_cast<const int4*>(G.gp_node.p), reinterpret_cast<const double4*>(G.gp_wt.p),
+                           G.w2.p, G.y.p, (double*)nullptr, 0, G.ntp, G.s.p, part, G.nbk);
+    } else {
+        bias_launch_reduce(S, st, src, part);
+    }
+}

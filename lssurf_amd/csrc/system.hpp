@@ -363,6 +363,48 @@ struct BiasData {
     std::vector<int32_t> h_grp;     // the caller's groups (empty: none)
 };
 
+// Sensor bias grids eliminated from the CGNR normal equations (lsq_set_sensor_grids; sgrid.inc): the
+// data rows of grid s gain a bilinear interpolation β_i into the grid's nodes, the grid is held by
+// its constraint rows C_s.  A data row lies in at most one grid and C_s touches only its own nodes, so
+// the eliminated block M = BᵀW²B + K (K_s = C_sᵀC_s) is one dense SPD matrix per grid.  All grids'
+// nodes share one padded index space: grid s owns [poff[s], poff[s + 1]), npad_s = its nodes rounded
+// up to 64, identity on the padding; its npad_s × npad_s matrices start at moff[s].  The transpose by
+// node lists (sorted point, weight) in point order, so every sum has a fixed order: no atomics.
+constexpr int64_t SG_MAX_NODES = 2048;                      // LSQ_SGRID_MAX_NODES
+constexpr int64_t SG_MAX_FACTOR_BYTES = (int64_t)1 << 30;   // LSQ_SGRID_MAX_FACTOR_BYTES
+constexpr int SG_NBR = 9;                                   // distinct nodes that share a row with one node
+struct SgridData {
+    bool on = false;
+    bool solved = false;            // aval belongs to the last lsq_solve's x
+    int64_t ng = 0, npts = 0;       // grids, data rows
+    int64_t ntot = 0, ntp = 0;      // nodes of all grids, and with the padding
+    int64_t ngp = 0, nent = 0;      // rows that lie in a grid; transpose entries (weights ≠ 0)
+    int64_t ntile = 0, nk = 0;      // 64-column tiles of all grids; K's distinct entries
+    int64_t fsum = 0;               // Σ npad_s² (doubles of one set of dense matrices)
+    int nbk = 0;                    // workgroups (= partials) of −Σ s_k y_k
+    std::vector<int64_t> h_nn, h_npad, h_poff, h_moff;
+    DBuf<int64_t> tr_ptr;           // padded node -> first transpose entry (ntp + 1)
+    DBuf<int32_t> tr_pt;            // entry -> sorted point
+    DBuf<int32_t> tr_gp;            // entry -> grid point (position in gp_*)
+    DBuf<uint32_t> tr_slot;         // entry -> 4 × 8 bit: the grid point's corners' places among nbr of this node
+    DBuf<double> tr_w;              // entry -> β
+    DBuf<int32_t> gp_pt;            // grid point -> sorted point (ascending)
+    DBuf<int32_t> gp_node;          // 4 per grid point: padded nodes
+    DBuf<double> gp_wt;             // 4 per grid point: β (0 pads a dropped corner)
+    DBuf<int32_t> nbr;              // SG_NBR per padded node: the padded nodes it shares rows with (−1: none)
+    DBuf<int32_t> node_grid;        // padded node -> grid
+    DBuf<int64_t> poff, moff, npad, nn;   // per grid: first padded node, first matrix entry, padded size, nodes
+    DBuf<int32_t> tile_grid, tile_jb;   // tile -> grid, column block
+    DBuf<int64_t> k_pos;            // K entry -> position in the dense matrices
+    DBuf<double> k_val;
+    DBuf<double> w2;                // sorted point -> row scale² (per solve)
+    DBuf<double> M, Ri;             // per solve: M_s, then its Cholesky factor R_s in place; R_s⁻¹
+    DBuf<double> d0;                // padded node -> M's diagonal before the factorisation
+    DBuf<int> err;                  // per grid: a pivot that is not positive
+    DBuf<double> s, z, y;           // padded node: Bᵀ src, R⁻ᵀ s, M⁻¹ s of the last reduction
+    std::vector<double> aval;       // node -> grid value of the last solve
+};
+
 // Extra sparse rows behind the stencil rows (lsq_set_extra_rows; xrows.inc): ≤ XR_MAXW entries per
 // row, columns = full ids, values unweighted.  Staged on the host before the structured formation,
 // which merges duplicates, drops zeros and the columns the col map removes.  The device keeps the
@@ -538,6 +580,7 @@ struct System {
     DBuf<int32_t> dmf_perm, dmf_cell;   // sorted point -> data row; (y, x) cell -> first sorted point
     std::string cg_why;            // why not (when !cg_ok)
     BiasData bias;                  // eliminated data biases (lsq_set_data_bias; bias.inc)
+    SgridData sgrid;                // eliminated sensor bias grids (lsq_set_sensor_grids; sgrid.inc)
     XrData xr;                      // extra sparse rows behind the stencil rows (lsq_set_extra_rows; xrows.inc)
     CgDesc cgh{};
     DBuf<CgDesc> cgd;

@@ -1,0 +1,154 @@
+"""Sensor bias grids: a coarse 2-D grid of additive bias per listed sensor (sensor_grid_bias_params).
+
+Behaviour follows LSsurf/setup_sensor_grid_bias.py (:6-69).  The grid of a sensor spans the floor and
+the ceil of its data's x and y to `spacing`; it is named 'sensor_{sensor}_bias' and takes the columns
+from G_data.col_N on.  The sensor's data rows gain the bilinear interpolation into it.  The grid is
+held by 'grad2_' + name (expected_rms_grad2 / sqrt(Π delta)) when expected_rms_grad2 is given and by
+'mag_' + name (one row per node, expected expected_rms, prior expected_val) when expected_rms is given,
+appended to the constraint list in that order.  A sensor without data adds nothing.  expected_rms_grad,
+filename and dims are accepted and ignored, as there.
+
+sensor_grid_device_form gives what the device's elimination takes (lsq_set_sensor_grids): per data row
+its grid, four local nodes and weights, and per grid the weighted constraint normal matrix
+K = CᵀC as triplets.
+"""
+import numpy as np
+import scipy.sparse as sp
+
+from . import containers as pc
+from .fd_grid import fd_grid
+from .lin_op import lin_op
+
+_PREFIX, _SUFFIX = 'sensor_', '_bias'
+
+
+def grid_name(sensor):
+    return f'{_PREFIX}{sensor}{_SUFFIX}'
+
+
+def is_sensor_grid(name):
+    return name.startswith(_PREFIX) and name.endswith(_SUFFIX) and len(name) >= len(_PREFIX) + len(_SUFFIX)
+
+
+def _snapped(v, step):
+    """[lo, hi]: the span of v widened to whole multiples of step"""
+    return [np.floor(v.min() / step) * step, np.ceil(v.max() / step) * step]
+
+
+def _uniform(value, n):
+    return np.full(int(n), float(value))
+
+
+def _curvature_op(grid, sigma):
+    """second differences of the grid (lin_op.grad2), each expected sigma per root of the cell area"""
+    op = lin_op(grid, name='grad2_' + grid.name).grad2(DOF=grid.name)
+    op.expected = _uniform(sigma / np.sqrt(np.prod(grid.delta)), op.N_eq)
+    return op
+
+
+def _magnitude_op(grid, sigma, centre):
+    """one row per node: the node's value, expected sigma around centre"""
+    nodes = np.arange(grid.N_nodes)
+    op = lin_op(grid, name='mag_' + grid.name).data_bias(ind=nodes, col=grid.col_0 + nodes)
+    op.expected = _uniform(sigma, op.N_eq)
+    op.prior = _uniform(centre, op.N_eq)
+    return op
+
+
+def setup_sensor_grid_bias(data, grids, G_data, constraint_op_list, sensor=None, spacing=None, expected_rms=None,
+                           expected_val=0, expected_rms_grad2=None, **ignored):
+    """Add the grid of `sensor` to grids, its interpolation to G_data and its constraints to
+    constraint_op_list; returns the grid's name, or None when the sensor has no data.  Further keys
+    (expected_rms_grad, filename, dims) are taken and not used."""
+    mine = np.flatnonzero(np.ravel(data.sensor) == sensor)
+    if mine.size == 0:
+        return None
+    y, x = np.ravel(data.y)[mine], np.ravel(data.x)[mine]
+    grid = fd_grid([_snapped(y, spacing), _snapped(x, spacing)], [spacing, spacing], name=grid_name(sensor),
+                   col_0=G_data.col_N)
+    grids[grid.name] = grid
+    # bilinear weights of the sensor's points, on the rows those points have among all the data
+    rows_op = lin_op(grid, name=grid.name).interp_mtx([y, x])
+    rows_op.r = mine[rows_op.r]
+    held_by = []
+    if expected_rms_grad2 is not None:
+        held_by.append(_curvature_op(grid, expected_rms_grad2))
+    if expected_rms is not None:
+        held_by.append(_magnitude_op(grid, expected_rms, expected_val))
+    constraint_op_list.extend(held_by)
+    G_data.add(rows_op)
+    return grid.name
+
+
+def parse_sensor_bias_grids(m0, G_data, grids):
+    """{name: grid container with x, y and z} of every sensor bias grid that has columns in G_data."""
+    out = {}
+    for name in G_data.TOC['cols']:
+        if not is_sensor_grid(name):
+            continue
+        g = grids[name]
+        z = np.asarray(m0)[G_data.TOC['cols'][name]].reshape(g.shape)
+        out[name] = pc.grid.data().from_dict({'x': g.ctrs[1], 'y': g.ctrs[0], 'z': z})
+    return out
+
+
+def check_sensor_grid_params(params_list):
+    """The keys lssurf_amd does not run: anything with jitter or stripe (they need DEM metadata files)."""
+    for params in params_list:
+        for key in params:
+            if 'jitter' in str(key) or 'stripe' in str(key):
+                raise NotImplementedError(f"smooth_fit: sensor_grid_bias_params key {key!r} needs DEM metadata files "
+                                          f"and is outside lssurf_amd")
+
+
+def sensor_grid_device_form(data, grids, sensor_of, constraint_ops):
+    """What lsq_set_sensor_grids takes for the grids of sensor_of ({name: sensor}, in column order): dict with
+    grid (rows,) int32 (−1: none), node (rows, 4) int32 local to the grid, wt (rows, 4), n_nodes per
+    grid, K = [(r, c, v)] per grid (triplets of CᵀC, C the grid's constraint rows over its expected
+    values, columns local) and shift per grid: the uniform prior of its magnitude rows (0 without)."""
+    n = int(np.size(data.sensor))
+    gid = np.full(n, -1, dtype=np.int32)
+    node = np.zeros((n, 4), dtype=np.int32)
+    wt = np.zeros((n, 4))
+    n_nodes, K, shift = [], [], []
+    sensor = np.ravel(data.sensor)
+    for s, name in enumerate(sensor_of):
+        g = grids[name]
+        rows = np.flatnonzero(sensor == sensor_of[name])
+        pts = [np.ravel(data.y)[rows], np.ravel(data.x)[rows]]
+        fsub = g.float_sub(pts)
+        cell = g.cell_sub_for_pts(pts)
+        fy, fx = fsub[0] - cell[0], fsub[1] - cell[1]
+        cy, cx = cell[0].astype(int), cell[1].astype(int)
+        gid[rows] = s
+        for k, (dy, dx) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
+            w = (fy if dy else 1. - fy) * (fx if dx else 1. - fx)
+            inside = (cy + dy < g.shape[0]) & (cx + dx < g.shape[1])   # a corner past the upper edge: weight 0
+            node[rows, k] = np.where(inside, (cy + dy) * g.shape[1] + cx + dx, 0)
+            wt[rows, k] = np.where(inside, w, 0.)
+        n_nodes.append(int(g.N_nodes))
+        rr, cc, vv, ev = [], [], [], 0.
+        row0 = 0
+        for op in constraint_ops:
+            if op.name not in ('grad2_' + name, 'mag_' + name):
+                continue
+            r, c, v = op.triplets()
+            rr.append(r + row0)
+            cc.append(c - g.col_0)
+            vv.append(v / np.ravel(op.expected)[r])
+            row0 += int(op.N_eq)
+            if op.name.startswith('mag_') and op.prior is not None:
+                prior = np.ravel(op.prior)
+                if np.any(prior != prior[0]):
+                    raise ValueError(f'sensor_grid_device_form: the prior of {op.name} is not uniform')
+                ev = float(prior[0])
+        if rr:
+            C = sp.csr_matrix((np.concatenate(vv), (np.concatenate(rr), np.concatenate(cc))),
+                              shape=(row0, int(g.N_nodes)))
+            Kc = (C.T @ C).tocoo()
+            K.append((Kc.row.astype(np.int32), Kc.col.astype(np.int32), Kc.data.astype(float)))
+        else:
+            K.append((np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0)))
+        shift.append(ev)
+    return dict(grid=gid, node=node, wt=wt, n_nodes=np.array(n_nodes, dtype=np.int64), K=K,
+                shift=np.array(shift, dtype=float), names=list(sensor_of))

@@ -20,6 +20,9 @@ last in Gc and the device carries them as extra rows inside matrix-free CGNR (ls
 With priors compute_E, n_gpus > 1 and lsq_bias='eliminate' raise NotImplementedError.
 lsq_prior_mg=True lets the multigrid preconditioner (precond 4) carry them, lumped into its coarse levels.
 Slope biases (data_slope_sensors) go with the data biases: they need bias_params and lsq_bias.
+Sensor bias grids (sensor_grid_bias_params; setup_sensor_grid_bias.py) run under the same key lsq_bias:
+'eliminate' (one dense block per grid eliminated inside CGNR, lsq_set_sensor_grids; not together with
+bias_params, data_slope_sensors or priors), 'columns' or 'auto'.
 Data biases (bias_params) run when the solver key lsq_bias says how: 'eliminate' (the device
 eliminates them inside CGNR, lsq_set_data_bias), 'columns' (ordinary columns of a generic system)
 or 'auto' (with priors: 'columns', with a warning where it would have eliminated).
@@ -42,6 +45,8 @@ from .lin_op import known_range, lin_op, toc_range
 from ._native import NativeError
 from .assemble import describe, extra_rows_of
 from .match_priors import match_prior_dz, match_tile_edges
+from .setup_sensor_grid_bias import check_sensor_grid_params, parse_sensor_bias_grids, \
+    sensor_grid_device_form, setup_sensor_grid_bias
 from .solver import LSQSolver
 
 DEFAULTS = {'reference_epoch': 0, 'W_ctr': 1e4, 'return_fit_objects': False, 'mask_file': None,
@@ -68,8 +73,7 @@ DEFAULTS = {'reference_epoch': 0, 'W_ctr': 1e4, 'return_fit_objects': False, 'ma
             # lumped into its coarse levels (opt-in; without priors the key does nothing)
             'lsq_prior_mg': False}
 
-OUT_OF_SCOPE = ('sensor_grid_bias_params', 'lagrangian_coords',
-                'constraint_scaling_maps', 'mask_file', 'bias_edit_vals')
+OUT_OF_SCOPE = ('lagrangian_coords', 'constraint_scaling_maps', 'mask_file', 'bias_edit_vals')
 
 
 class FitSystem:
@@ -77,8 +81,15 @@ class FitSystem:
     Ip_c as a column map; rows re-weighted / re-selected per outer iteration."""
 
     def __init__(self, G_data, Gc, keep_cols, n_full, device=0, structured=True, grids=None, bias=None,
-                 extra_ops=None, extra_csr=None, extra_mg=False):
-        """bias = (ids, c): eliminated data biases (LSQSolver.set_data_bias) — G_data and Gc are then
+                 extra_ops=None, extra_csr=None, extra_mg=False, sensor_grids=None):
+        """sensor_grids: the dict of setup_sensor_grid_bias.sensor_grid_device_form — eliminated sensor
+        bias grids (LSQSolver.set_sensor_grids), not together with bias.  G_data and Gc are the
+        operators without the grids' columns and constraint rows, the caller's row weights and rhs may
+        carry the grids' constraint rows behind them, and the grids take the columns after n_full in
+        expand().  A grid's uniform magnitude prior (shift) never reaches the device: the rhs of the
+        grid's rows loses it and the returned grid gains it (a row's weights sum to 1 and grad2 of a
+        constant is 0, so this is exact).
+        bias = (ids, c): eliminated data biases (LSQSolver.set_data_bias) — G_data and Gc are then
         the grid-only operators, the caller's row weights and rhs may carry further (bias
         constraint) rows behind them, and the biases take the columns after n_full in expand().
         bias = (ids, c, (group, u, c_slope)): slope biases too (LSQSolver.set_data_slope): group per
@@ -198,6 +209,29 @@ class FitSystem:
             except Exception:
                 self.solver.close()
                 raise
+        self.sg, self.sg_vals = None, None
+        if sensor_grids is not None:
+            if bias is not None:
+                self.solver.close()
+                raise ValueError('FitSystem: sensor_grids and bias do not go together')
+            # matrix-free CGNR only, never the dense preconditioner (LSQR).  Unlike the biases the grids leave
+            # the multigrid its iteration count (58 → 64 at C4, profiles/sgrid_c4.json), so 'auto' keeps it
+            self.dense_ok = False
+            try:
+                sg = dict(sensor_grids)
+                sg['grid'] = np.asarray(sg['grid']).astype(np.int32)
+                self.solver.set_sensor_grids(sg['grid'], sg['node'], sg['wt'], sg['n_nodes'], sg['K'])
+            except Exception:
+                self.solver.close()
+                raise
+            self.sg = sg
+            self.sg_off = np.concatenate([[0], np.cumsum(sg['n_nodes'])]).astype(np.int64)
+            self.sg_vals = np.zeros(int(self.sg_off[-1]))
+            on = sg['grid'] >= 0
+            self.sg_rows = np.flatnonzero(on)
+            self.sg_cols = self.sg_off[sg['grid'][on]][:, None] + np.asarray(sg['node'])[on]
+            self.sg_wt = np.asarray(sg['wt'], dtype=float)[on]
+            self.sg_row_shift = np.asarray(sg['shift'], dtype=float)[sg['grid'][on]]
 
     @property
     def blocks(self):
@@ -238,13 +272,18 @@ class FitSystem:
             self._mask[:self.n_data] = dk
             self.solver.set_row_mask(self._mask)
             self._keep_last = dk.copy()
-        if self.bias_ids is not None:   # the device rows are a prefix of the caller's rows
+        if self.bias_ids is not None or self.sg is not None:   # the device rows are a prefix of the caller's rows
             rhs = rhs[:self.n_data + self.n_con]
+        if self.sg is not None and np.any(self.sg_row_shift):   # a = a' + shift: the device sees zero priors
+            rhs = rhs.copy()
+            rhs[self.sg_rows] -= self.sg_row_shift
         x, self.stats = self.solver.solve(rhs, x0=x0, b_rows=getattr(self, 'b_rows', 0), **opts)
         if self.bias_ids is not None:
             self.bias_vals = self.solver.data_bias()
         if self.slope_grp is not None:
             self.slope_vals = self.solver.data_slope()
+        if self.sg is not None:
+            self.sg_vals = self.solver.sensor_grids() + np.repeat(self.sg['shift'], self.sg['n_nodes'])
         return x
 
     def expand(self, x):
@@ -254,6 +293,9 @@ class FitSystem:
             m0[self.n_full:self.n_full + self.bias_vals.size] = self.bias_vals
             if n_slope:   # behind the biases, (x, y) per group
                 m0[self.n_full + self.bias_vals.size:] = self.slope_vals.ravel()
+        elif self.sg is not None:       # the grids of the last solve, in the columns after the others
+            m0 = np.zeros(self.n_full + self.sg_vals.size)
+            m0[self.n_full:] = self.sg_vals
         else:
             m0 = np.zeros(self.n_full)
         m0[self.keep_cols] = x
@@ -268,6 +310,8 @@ class FitSystem:
         if self.slope_grp is not None:
             on = self.slope_grp >= 0
             y[on] += np.sum(self.slope_u[on] * self.slope_vals[self.slope_grp[on]], axis=1)
+        if self.sg is not None:
+            y[self.sg_rows] += np.sum(self.sg_wt * self.sg_vals[self.sg_cols], axis=1)
         return y
 
     def rows_sumsq(self, x, ranges):
@@ -577,7 +621,7 @@ def parse_model(m, m0, data, R, RMS, G_data, averaging_ops, Gc, Ec, grids, args,
         m[key] = pc.grid.data().from_dict(fields)
     m['all'] = m0
     m['extent'] = np.concatenate((z0g.bds[1], z0g.bds[0]))
-    m['sensor_bias_grids'] = {}
+    m['sensor_bias_grids'] = parse_sensor_bias_grids(m0, G_data, grids)
     m['jitter_bias_grids'] = {}
     if system is None or not _device_constraint_stats(system, m0, Gc, R, RMS):
         if callable(Ec):         # smooth_fit's on-demand constraint sigma
@@ -681,6 +725,31 @@ def _bias_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, bias_model, m
     return FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=device, grids=grids)
 
 
+def _sgrid_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, sgrid_sensor, constraint_op_list, mode, grids,
+                      device, args):
+    """The device system of a fit with sensor bias grids (and no biases, slopes or priors).
+    'eliminate': the operators without the grids on the device plus lsq_set_sensor_grids (the grids'
+    constraint rows are the last rows of Gc, so the device rows are a prefix of the host rows);
+    'columns': the grids as ordinary columns of a generic (COO-formed) system; 'auto': 'columns' when
+    the other unknowns are few enough for the dense preconditioner, when the options ask for what only
+    'columns' runs (LSQR, the dense preconditioner) or when the device refuses (no matrix-free data
+    rows, a grid over the size cap), else 'eliminate'."""
+    n_grid = G_grid.col_N if G_grid is not None else None
+    if mode == 'auto' and (describe(G_grid, Gc_grid, with_fields=True) is None or
+                           np.count_nonzero(keep_cols < n_grid) <= args['lsq_dense_max'] or
+                           args['lsq_method'] == 'lsqr' or args['lsq_precond'] == 2):
+        mode = 'columns'
+    if mode != 'columns':
+        sg = sensor_grid_device_form(data, grids, sgrid_sensor, constraint_op_list)
+        try:
+            return FitSystem(G_grid, Gc_grid, keep_cols[keep_cols < n_grid], n_grid, device=device, grids=grids,
+                             sensor_grids=sg)
+        except NativeError:
+            if mode == 'eliminate':
+                raise
+    return FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=device, grids=grids)
+
+
 def smooth_fit(**kwargs):
     required = ('data', 'W', 'ctr', 'spacing', 'E_RMS')
     args = dict(DEFAULTS)
@@ -722,6 +791,38 @@ def smooth_fit(**kwargs):
                                       "4; the dense preconditioner needs lsq_bias='columns'")
 
     has_priors = args.get('prior_args') is not None or args.get('prior_edge_args') is not None
+    has_sgrids = args.get('sensor_grid_bias_params') is not None and len(args['sensor_grid_bias_params']) > 0
+    sgrid_mode = None
+    if has_sgrids:
+        # sensor bias grids: the same key says how they run, and the refusals of bias_params hold
+        sgrid_mode = bias_mode
+        if sgrid_mode is None:
+            raise NotImplementedError("smooth_fit: 'sensor_grid_bias_params' needs the solver key lsq_bias ('eliminate', "
+                                      "'columns' or 'auto'); without it sensor bias grids are outside lssurf_amd")
+        if sgrid_mode not in ('eliminate', 'columns', 'auto'):
+            raise ValueError(f"smooth_fit: lsq_bias must be 'eliminate', 'columns' or 'auto', not {sgrid_mode!r}")
+        check_sensor_grid_params(args['sensor_grid_bias_params'])
+        if args['compute_E']:
+            raise NotImplementedError("smooth_fit: compute_E with sensor_grid_bias_params is outside lssurf_amd")
+        if int(args['n_gpus']) > 1 or (args['devices'] is not None and len(args['devices']) > 1):
+            raise NotImplementedError("smooth_fit: sensor_grid_bias_params runs on one GPU")
+        if sgrid_mode == 'eliminate' and args['lsq_method'] == 'lsqr':
+            raise NotImplementedError("smooth_fit: lsq_bias='eliminate' runs CGNR; lsq_method='lsqr' needs "
+                                      "lsq_bias='columns'")
+        if sgrid_mode == 'eliminate' and args['lsq_precond'] not in ('auto', 1, 3, 4):
+            raise NotImplementedError("smooth_fit: lsq_bias='eliminate' runs CGNR with lsq_precond 'auto', 1, 3 or "
+                                      "4; the dense preconditioner needs lsq_bias='columns'")
+        if args['bias_params'] is not None or has_slopes or has_priors:
+            # the joint eliminated block is no longer one dense block per grid
+            if sgrid_mode == 'eliminate':
+                raise NotImplementedError("smooth_fit: sensor_grid_bias_params with lsq_bias='eliminate' does not go "
+                                          "together with bias_params, data_slope_sensors or priors; "
+                                          "lsq_bias='columns' (or 'auto') carries them all")
+            if sgrid_mode == 'auto':
+                warnings.warn("smooth_fit: lsq_bias='auto' with sensor_grid_bias_params beside bias_params, "
+                              "data_slope_sensors or priors takes 'columns': a generic (COO-formed) system, not "
+                              "matrix-free CGNR", RuntimeWarning, stacklevel=2)
+                sgrid_mode = bias_mode = 'columns'
     if has_priors:
         # priors (match_priors): rows behind the constraints that the device carries as extra rows
         if args['compute_E']:
@@ -805,6 +906,26 @@ def smooth_fit(**kwargs):
                 G_data.add(G_slope)
                 constraint_op_list.append(Gc_slope)
                 zero_prior.add(Gc_slope.name)
+    # sensor bias grids: a grid's columns behind everything so far and its constraint rows behind the
+    # constraints so far, grid by grid (smooth_fit.py:570-572).  G_grid / Gc_grid: the operators
+    # without them, which the device holds when it eliminates the grids itself
+    sgrid_sensor = {}
+    if has_sgrids:
+        if sgrid_mode != 'columns':
+            G_grid = interp_ops()
+            Gc_grid = lin_op(None, name='constraints').vstack(list(constraint_op_list))
+        for params in args['sensor_grid_bias_params']:
+            n_before = len(constraint_op_list)
+            name = setup_sensor_grid_bias(data, grids, G_data, constraint_op_list, **params)
+            if name is not None:
+                sgrid_sensor[name] = params['sensor']
+            for op in constraint_op_list[n_before:]:
+                if op.prior is None:
+                    op.prior = np.zeros(np.shape(op.expected))
+                    zero_prior.add(op.name)
+        if not sgrid_sensor:
+            has_sgrids, sgrid_mode = False, None
+    sgrid_ops = {'grad2_' + name for name in sgrid_sensor} | {'mag_' + name for name in sgrid_sensor}
     # priors, in the reference's order (smooth_fit.py:575-582), behind every other constraint
     prior_ops = []
     if args.get('prior_args') is not None:
@@ -834,6 +955,7 @@ def smooth_fit(**kwargs):
     rhs[0:data.size] = data.z.ravel()
     b_rows = data.size   # rhs[b_rows:] == 0: only the data rows (and non-zero priors) cross PCIe
     b_rows_all = None    # the same with the prior ops counted (systems that hold them as ordinary rows)
+    b_rows_sg = None     # and with the sensor grids' magnitude priors (systems that hold them as ordinary rows)
     for op in constraint_op_list:   # rhs[data.size:] = the concatenated priors
         if op.name not in zero_prior:
             rows = _toc_slice(Gc, op.name)
@@ -847,6 +969,8 @@ def smooth_fit(**kwargs):
             if np.any(prior != 0):
                 if op.name in prior_names:   # the device uploads its extra rows' b itself
                     b_rows_all = max(b_rows_all or 0, data.size + end)
+                elif op.name in sgrid_ops:   # eliminated grids: the device never sees their prior
+                    b_rows_sg = max(b_rows_sg or 0, data.size + end)
                 else:
                     b_rows = max(b_rows, data.size + end)
     keep_cols = reference_epoch_keep_cols(G_data.col_N, grids['dz'], args['reference_epoch'])
@@ -855,8 +979,11 @@ def smooth_fit(**kwargs):
     if args['VERBOSE']:
         print('initial: %d:' % np.max(G_data.r), flush=True)
     if args['return_fit_objects']:
-        return {'data': data, 'G_data': G_data, 'Gc': Gc, 'grids': grids, 'Ed': Ed, 'Ec': Ec(),
-                'prior_ops': prior_ops, 'rhs': rhs}
+        out = {'data': data, 'G_data': G_data, 'Gc': Gc, 'grids': grids, 'Ed': Ed, 'Ec': Ec(),
+               'prior_ops': prior_ops, 'rhs': rhs}
+        if sgrid_sensor:   # what FitSystem(sensor_grids=) takes
+            out['sensor_grids'] = sensor_grid_device_form(data, grids, sgrid_sensor, constraint_op_list)
+        return out
 
     system = None
     try:
@@ -874,12 +1001,19 @@ def smooth_fit(**kwargs):
             elif bias_model:
                 system = _bias_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, bias_model,
                                           bias_mode, grids, devices[0], args, prior_ops=prior_ops)
+            elif has_sgrids and not prior_ops:
+                system = _sgrid_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, sgrid_sensor,
+                                           constraint_op_list, sgrid_mode, grids, devices[0], args)
             else:
                 system = FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=devices[0], grids=grids,
                                    extra_ops=prior_ops, extra_mg=bool(args['lsq_prior_mg']) and bool(prior_ops))
             if b_rows_all is not None and not getattr(system, 'n_extra', 0):
                 b_rows = max(b_rows, b_rows_all)
+            if b_rows_sg is not None and getattr(system, 'sg', None) is None:
+                b_rows = max(b_rows, b_rows_sg)
             system.b_rows = b_rows
+            if has_sgrids:   # how the sensor bias grids ran
+                timing['sensor_grids'] = 'eliminate' if getattr(system, 'sg', None) is not None else 'columns'
             timing['formation'] = getattr(system, 'formation', None)   # 'stencil' or 'coo'
             timing['extra_rows'] = int(getattr(system, 'n_extra', 0))  # prior rows the device holds as extra rows
             timing['device_setup'] = time() - tic

@@ -29,6 +29,7 @@ class LSQSolver:
         self.m = self.n = self.n_full = None
         self._n_bias = 0           # bias IDs set by set_data_bias
         self._n_slope = 0          # slope groups set by set_data_slope
+        self._sg_nodes = 0         # nodes of all grids set by set_sensor_grids
 
     # ---- lifetime --------------------------------------------------------------------------
     def close(self):
@@ -343,6 +344,50 @@ class LSQSolver:
         o = np.zeros(8)
         self._check(self._L.lsq_profile_data_slope(self._h, int(reps), int(precond), ptr(o)), 'lsq_profile_data_slope')
         return {k: (float(o[i]), float(o[4 + i])) for i, k in enumerate(('chunk', 'rank', 'group', 'apply'))}
+
+    def set_sensor_grids(self, grid, node, wt, n_nodes, K):
+        """A coarse grid of additive bias per sensor on the data rows, each eliminated as one dense
+        block inside CGNR (lsq_set_sensor_grids); not together with set_data_bias / set_data_slope.
+
+        grid: the grid of every data row (caller's row order), −1 for none, else in [0, len(n_nodes));
+        node, wt: (rows, 4) nodes local to the row's grid and their weights (weight 0 pads a dropped
+        corner), read where grid ≥ 0; n_nodes: nodes per grid; K: per grid the triplets (r, c, v) of
+        its weighted constraint normal matrix CᵀC.  grid = None (or no grids) clears them."""
+        if grid is None or n_nodes is None or np.size(n_nodes) == 0:
+            self._check(self._L.lsq_set_sensor_grids(self._h, 0, None, None, None, 0, None, None, None, None, None),
+                        'lsq_set_sensor_grids')
+            self._sg_nodes = 0
+            return
+        grid = as_c(grid, np.int32)
+        node = as_c(node, np.int32)
+        wt = as_c(wt, np.float64)
+        n_nodes = as_c(n_nodes, np.int64)
+        if node.size != 4 * grid.size or wt.size != 4 * grid.size or len(K) != n_nodes.size:
+            raise ValueError('set_sensor_grids: node and wt must hold four values per row and K one entry per grid')
+        k_ptr = np.zeros(n_nodes.size + 1, np.int64)
+        np.cumsum([np.size(k[0]) for k in K], out=k_ptr[1:])
+        k_row = as_c(np.concatenate([np.ravel(k[0]) for k in K]) if k_ptr[-1] else np.zeros(1), np.int32)
+        k_col = as_c(np.concatenate([np.ravel(k[1]) for k in K]) if k_ptr[-1] else np.zeros(1), np.int32)
+        k_val = as_c(np.concatenate([np.ravel(k[2]) for k in K]) if k_ptr[-1] else np.zeros(1), np.float64)
+        self._check(self._L.lsq_set_sensor_grids(self._h, grid.size, ptr(grid), ptr(node), ptr(wt), n_nodes.size,
+                                                 ptr(n_nodes), ptr(k_ptr), ptr(k_row), ptr(k_col), ptr(k_val)),
+                    'lsq_set_sensor_grids')
+        self._sg_nodes = int(n_nodes.sum())
+
+    def sensor_grids(self):
+        """The grids' node values that belong to the last solve's x, grid after grid."""
+        a = np.zeros(max(self._sg_nodes, 1))
+        self._check(self._L.lsq_get_sensor_grids(self._h, ptr(a)), 'lsq_get_sensor_grids')
+        return a[:self._sg_nodes]
+
+    def profile_sensor_grids(self, reps=10, precond=3):
+        """Per-kernel times of the sensor grids' elimination inside real iterations of the live
+        iterate() state: {name: (ms, algorithmic bytes)} for s = Bᵀtd, the two triangular products
+        and the apply pass (lsq_profile_sensor_grids)."""
+        o = np.zeros(8)
+        self._check(self._L.lsq_profile_sensor_grids(self._h, int(reps), int(precond), ptr(o)),
+                    'lsq_profile_sensor_grids')
+        return {k: (float(o[i]), float(o[4 + i])) for i, k in enumerate(('btd', 'trsv_t', 'trsv', 'apply'))}
 
     def info(self):
         o = np.zeros(8, np.int64)

@@ -1,0 +1,408 @@
+"""Sensor bias grids eliminated inside CGNR (lsq_set_sensor_grids; csrc/sgrid.inc) and smooth_fit's
+sensor_grid_bias_params.
+
+Operator: lsq_normal_apply with grids set must equal AᵀA p − A_dᵀ W B M⁻¹ Bᵀ W A_d p with
+M = BᵀW²B + K formed densely on the host from the assembled, weighted, row-selected A, to the normal
+operator's own tolerance, 1e-12 of max|q|, on the layouts that can break the sums.  The host asserts
+cond(M_s) ≤ 1e6 there, so the tolerance means something.  Solves: the reference's recorded system
+(tests/golden/sys_sgrid.npz, gen_golden_sgrid.py) within REL 1e-6 / ABS 1e-4; smooth_fit against the
+reference's outputs with the tolerances of test_gpu_bias.py."""
+import functools
+
+import numpy as np
+import pytest
+
+import lssurf_amd as LS
+from conftest import golden, golden_kwargs, golden_points
+from lssurf_amd._native import NativeError
+from lssurf_amd.constraint_functions import reference_epoch_keep_cols
+from lssurf_amd.smooth_fit import FitSystem
+from test_gpu_cgnr import _synthetic_system
+
+pytestmark = pytest.mark.gpu
+REL, ABS = 1e-6, 1e-4
+TOL = dict(atol=1e-12, btol=1e-12, conlim=1e12)
+NAMES = ['sensor_1.0_bias', 'sensor_2.0_bias']
+MAX_NODES = 2048
+
+
+def _cells(shape, n, rng, edge=0):
+    """(node (n, 4), wt (n, 4)) of n points in random cells of a lattice of `shape` nodes; the last
+    `edge` of them on the lattice's upper edges (their far corners are dropped: weight 0).  A
+    one-node-wide lattice has no cells along that side: every point sits on it."""
+    ny, nx = shape
+    cy = rng.integers(0, max(ny - 1, 1), n)
+    cx = rng.integers(0, max(nx - 1, 1), n)
+    fy = rng.random(n) if ny > 1 else np.zeros(n)
+    fx = rng.random(n) if nx > 1 else np.zeros(n)
+    if edge:
+        cy[-edge:], fy[-edge:] = ny - 1, 0.
+        cx[-edge // 2:], fx[-edge // 2:] = nx - 1, 0.
+    node = np.zeros((n, 4), np.int32)
+    wt = np.zeros((n, 4))
+    for k, (dy, dx) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
+        inside = (cy + dy < ny) & (cx + dx < nx)
+        w = (fy if dy else 1. - fy) * (fx if dx else 1. - fx)
+        node[:, k] = np.where(inside, (cy + dy) * nx + cx + dx, 0)
+        wt[:, k] = np.where(inside, w, 0.)
+    return node, wt
+
+
+def _K(shape, rng, mag=(0.5, 3.), curv=1.0):
+    """Triplets of CᵀC for magnitude rows (one per node) and second differences along x."""
+    ny, nx = shape
+    nn = ny * nx
+    C = [np.diag(rng.uniform(*mag, nn))]
+    for y in range(ny):
+        for x in range(1, nx - 1):
+            row = np.zeros(nn)
+            row[y * nx + x - 1:y * nx + x + 2] = curv * np.array([1., -2., 1.])
+            C.append(row[None, :])
+    C = np.vstack(C)
+    K = C.T @ C
+    r, c = np.nonzero(K)
+    return r.astype(np.int32), c.astype(np.int32), K[r, c]
+
+
+def _layout(npts, shapes, sizes, rng, edge=0):
+    """Grids of `shapes` over sizes[s] rows each, dealt out by a random permutation of the points (no
+    grid is contiguous in the solver's cell-sorted order, and the grids overlap in space)."""
+    grid = np.full(npts, -1, np.int32)
+    node = np.zeros((npts, 4), np.int32)
+    wt = np.zeros((npts, 4))
+    order = rng.permutation(npts)
+    k = 0
+    for s, (shape, n) in enumerate(zip(shapes, sizes)):
+        rows = order[k:k + n]
+        k += n
+        grid[rows] = s
+        node[rows], wt[rows] = _cells(shape, n, rng, edge=min(edge, n))
+    n_nodes = np.array([a * b for a, b in shapes], np.int64)
+    return grid, node, wt, n_nodes, [_K(shape, rng) for shape in shapes]
+
+
+def _layouts(npts, keep, rng):
+    """name -> (grid, node, wt, n_nodes, K)"""
+    out = {}
+    # grids of 63, 64 and 65 nodes (the padding's edge) and one of 1 × 2 nodes, some rows on the upper edges
+    out['sizes'] = _layout(npts, [(7, 9), (8, 8), (5, 13), (1, 2)], [900, 700, 800, 150], rng, edge=40)
+    # nodes with exactly 0, 1, 63, 64 and 65 entries: points that sit on a node (three corners dropped)
+    shape = (2, 5)
+    counts = [0, 1, 63, 64, 65, 0, 2, 0, 130, 7]
+    grid, node, wt, n_nodes, K = _layout(npts, [shape, (3, 4)], [sum(counts), 300], rng)
+    rows = np.flatnonzero(grid == 0)
+    node[rows], wt[rows] = 0, 0.
+    node[rows, 0] = np.repeat(np.arange(10), counts)
+    wt[rows, 0] = 1.
+    out['counts'] = (grid, node, wt, n_nodes, K)
+    # a grid all of whose rows are masked (M = K): the masked rows are grid 0
+    g_m = np.where(keep, 1 + rng.integers(0, 2, npts), 0).astype(np.int32)
+    grid, node, wt, n_nodes, K = _layout(npts, [(4, 4), (6, 5), (3, 7)], [0, 0, 0], rng)
+    for s, shape in enumerate([(4, 4), (6, 5), (3, 7)]):
+        rows = np.flatnonzero(g_m == s)
+        node[rows], wt[rows] = _cells(shape, rows.size, rng)
+    out['masked_grid'] = (g_m, node, wt, n_nodes, K)
+    # a grid in [0, ng) that no row carries
+    out['empty_grid'] = _layout(npts, [(4, 6), (3, 3), (5, 5)], [1000, 0, 1200], rng)
+    # every row outside every grid
+    out['none'] = _layout(npts, [(4, 4), (2, 3)], [0, 0], rng)
+    if npts >= 30000:
+        # nodes with more than 64 · 32 entries: 1 × 2 nodes under 6 000 rows, 3 × 3 under 20 000
+        out['long'] = _layout(npts, [(1, 2), (3, 3), (9, 9)], [6000, 20000, 3000], rng, edge=100)
+    return out
+
+
+def _dense_B(grid, node, wt, n_nodes):
+    off = np.concatenate([[0], np.cumsum(n_nodes)])
+    B = np.zeros((grid.size, int(off[-1])))
+    on = np.flatnonzero(grid >= 0)
+    for q in range(4):
+        np.add.at(B, (on, off[grid[on]] + node[on, q]), wt[on, q])
+    return B, off
+
+
+def _dense_K(n_nodes, K, off):
+    Kd = np.zeros((int(off[-1]), int(off[-1])))
+    for s, (r, c, v) in enumerate(K):
+        np.add.at(Kd, (off[s] + r, off[s] + c), v)
+    return Kd
+
+
+def _host_reduced(A, n_kept, Wk, keep, layout, pc):
+    """((AᵀA − A_dᵀ W B M⁻¹ Bᵀ W A_d) p, cond(M_s) per grid) from the assembled, weighted,
+    row-selected A (data rows first) with B and M dense."""
+    grid, node, wt, n_nodes, K = layout
+    Ad = A[:n_kept]
+    t = Ad @ pc                                               # W A_d p
+    B, off = _dense_B(grid[keep], node[keep], wt[keep], n_nodes)
+    BW = Wk[:, None] * B
+    M = BW.T @ BW + _dense_K(n_nodes, K, off)
+    conds = [np.linalg.cond(M[off[s]:off[s + 1], off[s]:off[s + 1]]) for s in range(n_nodes.size)]
+    blocks = M.copy()
+    for s in range(n_nodes.size):
+        blocks[off[s]:off[s + 1], off[s]:off[s + 1]] = 0
+    assert not blocks.any()                                   # one block per grid
+    sol = np.linalg.solve(M, BW.T @ t)
+    return A.T @ (A @ pc) - Ad.T @ (BW @ sol), conds
+
+
+def _entry_counts(layout):
+    grid, node, wt, n_nodes, K = layout
+    B, off = _dense_B(grid, node, wt, n_nodes)
+    return (B != 0).sum(axis=0)
+
+
+@pytest.mark.parametrize('which', ['t64', 'tdense'])
+def test_reduced_normal_operator(gpu_available, which):
+    S, fs, w, rhs = _synthetic_system(which)
+    rng = np.random.default_rng(31)
+    keep = rng.random(fs.n_data) > 0.2
+    try:
+        fs.solver.set_row_weight(w)
+        fs.solver.set_row_mask(np.concatenate([keep, np.ones(fs.n_con, bool)]))
+        ok, why = fs.solver.cg_available(1)
+        assert ok, why
+        A = fs.solver.get_csr()          # before anything is set: the grid operator
+        n_kept = int(keep.sum())
+        Wk = w[:fs.n_data][keep]
+        pc = rng.standard_normal(A.shape[1])
+        pf = np.zeros(fs.n_full)
+        pf[fs.keep_cols] = pc
+        q_plain = fs.solver.normal_apply(pf)[fs.keep_cols]
+        layouts = _layouts(fs.n_data, keep, rng)
+        assert ('long' in layouts) == (which == 'tdense')
+        if which == 'tdense':            # the small system runs the others
+            layouts = {k: layouts[k] for k in ('long', 'sizes')}
+            assert _entry_counts(layouts['long']).max() > 64 * 32
+        else:
+            assert list(_entry_counts(layouts['counts'])[:5]) == [0, 1, 63, 64, 65]
+            assert list(layouts['sizes'][3]) == [63, 64, 65, 2]
+        for name, layout in layouts.items():
+            tag = f'{which} {name}'
+            fs.solver.set_sensor_grids(*layout)
+            ok, why = fs.solver.cg_available(1)
+            assert ok, (tag, why)
+            q = fs.solver.normal_apply(pf)[fs.keep_cols]
+            qr, conds = _host_reduced(A, n_kept, Wk, keep, layout, pc)
+            assert max(conds) <= 1e6, (tag, conds)
+            err = np.abs(q - qr).max() / np.abs(qr).max()
+            acted = np.abs(q - q_plain).max() / np.abs(qr).max()
+            print(f'{tag}: err {err:.2e} (limit 1e-12), max cond(M_s) {max(conds):.2e}, grids change q by {acted:.2e}')
+            assert err <= 1e-12, (tag, err)
+            if name == 'none':           # no row in any grid: the grids cannot act
+                assert np.array_equal(q, q_plain), tag
+            else:
+                assert acted > 1e-9, (tag, acted)
+            assert np.array_equal(q, fs.solver.normal_apply(pf)[fs.keep_cols]), tag   # run to run
+    finally:
+        fs.close()
+
+
+def test_refusals_leave_the_handle_unchanged(gpu_available):
+    S, fs, w, rhs = _synthetic_system('t64')
+    rng = np.random.default_rng(32)
+    keep = rng.random(fs.n_data) > 0.1
+    grid, node, wt, n_nodes, K = _layouts(fs.n_data, keep, rng)['sizes']
+    try:
+        x0 = fs.solve(w, keep, rhs, precond=3, method=1, **TOL)
+        it0 = fs.stats['iters']
+        i = int(np.flatnonzero(grid == 1)[0])
+        bad = node.copy()
+        bad[i, 2] = n_nodes[1]
+        with pytest.raises(NativeError, match='node'):
+            fs.solver.set_sensor_grids(grid, bad, wt, n_nodes, K)
+        bad[i, 2] = -1
+        with pytest.raises(NativeError, match='node'):
+            fs.solver.set_sensor_grids(grid, bad, wt, n_nodes, K)
+        for v in (len(n_nodes), -2):
+            with pytest.raises(NativeError, match='outside'):
+                fs.solver.set_sensor_grids(np.where(np.arange(grid.size) == i, v, grid), node, wt, n_nodes, K)
+        wb = wt.copy()
+        wb[i, 1] = np.nan
+        with pytest.raises(NativeError, match='finite'):
+            fs.solver.set_sensor_grids(grid, node, wb, n_nodes, K)
+        with pytest.raises(NativeError, match='npts'):
+            fs.solver.set_sensor_grids(grid[:-1], node[:-1], wt[:-1], n_nodes, K)
+        big = n_nodes.copy()
+        big[0] = MAX_NODES + 1
+        with pytest.raises(NativeError, match='cap'):
+            fs.solver.set_sensor_grids(grid, node, wt, big, K)
+        with pytest.raises(NativeError, match='cap'):   # 64 grids of 2048 nodes: 2 GiB of inverse factors
+            fs.solver.set_sensor_grids(grid, node, wt, np.full(64, MAX_NODES, np.int64), [K[3]] * 64)
+        Kb = list(K)
+        Kb[2] = (K[2][0], np.where(np.arange(K[2][1].size) == 0, n_nodes[2], K[2][1]).astype(np.int32), K[2][2])
+        with pytest.raises(NativeError, match='K'):
+            fs.solver.set_sensor_grids(grid, node, wt, n_nodes, Kb)
+        with pytest.raises(NativeError):
+            fs.solver.sensor_grids()           # none set
+        # biases already set
+        fs.solver.set_data_bias(rng.integers(0, 3, fs.n_data), np.ones(3))
+        with pytest.raises(NativeError, match='biases'):
+            fs.solver.set_sensor_grids(grid, node, wt, n_nodes, K)
+        fs.solver.set_data_bias(None, None)
+        # the refused calls set nothing: the same bits as before
+        assert np.array_equal(fs.solve(w, keep, rhs, precond=3, method=1, **TOL), x0) and fs.stats['iters'] == it0
+        # values outside every grid are never read
+        wn, nd = wt.copy(), node.copy()
+        wn[grid < 0], nd[grid < 0] = np.nan, -7
+        fs.solver.set_sensor_grids(grid, nd, wn, n_nodes, K)
+        with pytest.raises(NativeError, match='no lsq_solve'):
+            fs.solver.sensor_grids()           # set, not solved
+        with pytest.raises(NativeError, match='sensor grids'):
+            fs.solver.set_data_bias(rng.integers(0, 3, fs.n_data), np.ones(3))
+        with pytest.raises(NativeError, match='CGNR'):
+            fs.solve(w, keep, rhs, precond=3, method=0, **TOL)
+        xs = fs.solve(w, keep, rhs, precond=3, method=1, **TOL)
+        assert np.all(np.isfinite(xs)) and np.any(xs != x0) and np.any(fs.solver.sensor_grids() != 0)
+        # a grid held by its curvature only, all of whose rows are masked: M = K is singular
+        r, c, v = _K((7, 9), rng, mag=(0., 0.))
+        keep_m = keep & (grid != 0)
+        fs.solver.set_sensor_grids(grid, node, wt, n_nodes, [(r, c, v)] + list(K[1:]))
+        with pytest.raises(NativeError, match='sensor grid 0'):
+            fs.solve(w, keep_m, rhs, precond=3, method=1, **TOL)
+    finally:
+        fs.close()
+
+
+def test_clearing_the_grids_restores_every_bit(gpu_available):
+    res = []
+    for with_grids in (False, True):
+        S, fs, w, rhs = _synthetic_system('t64')
+        keep = np.random.default_rng(34).random(fs.n_data) > 0.1
+        layout = _layouts(fs.n_data, keep, np.random.default_rng(35))['sizes']
+        try:
+            if with_grids:
+                fs.solver.set_sensor_grids(*layout)
+                xs = fs.solve(w, keep, rhs, precond=3, method=1, **TOL)
+                a = fs.solver.sensor_grids()
+                assert np.array_equal(xs, fs.solve(w, keep, rhs, precond=3, method=1, **TOL))   # run to run
+                assert np.array_equal(a, fs.solver.sensor_grids())
+                fs.solver.set_sensor_grids(None, None, None, None, None)
+                with pytest.raises(NativeError):
+                    fs.solver.sensor_grids()
+            x = fs.solve(w, keep, rhs, precond=3, method=1, **TOL)
+            res.append((x, fs.stats['iters']))
+        finally:
+            fs.close()
+    assert np.any(xs != res[1][0])
+    assert np.array_equal(res[0][0], res[1][0]) and res[0][1] == res[1][1]
+
+
+@functools.lru_cache(maxsize=None)
+def _sgrid_objects():
+    """Host objects of the reference's recorded system: the operators without the grids, the full
+    ones (which also hold the device form of the grids)."""
+    g = golden('sys_sgrid.npz')
+    kw = golden_kwargs(g)
+    kw_grid = {k: v for k, v in kw.items() if k != 'sensor_grid_bias_params'}
+    Sg = LS.smooth_fit(data=golden_points(g), return_fit_objects=True, **kw_grid)
+    Sf = LS.smooth_fit(data=golden_points(g), return_fit_objects=True, lsq_bias='columns', **kw)
+    assert Sf['sensor_grids']['names'] == NAMES
+    return g, kw, Sg, Sf
+
+
+def _weights_rhs(S):
+    w = 1. / np.concatenate((S['Ed'], S['Ec']))
+    rhs = np.zeros(w.size)
+    rhs[:S['data'].size] = S['data'].z
+    return w, rhs
+
+
+def test_eliminated_solve_reaches_the_oracle(gpu_available):
+    g, kw, Sg, Sf = _sgrid_objects()
+    xs = g['x']
+    n_sg = int(Sf['sensor_grids']['n_nodes'].sum())
+    n_grid = xs.size - n_sg
+    keep = reference_epoch_keep_cols(Sg['G_data'].col_N, Sg['grids']['dz'], kw['reference_epoch'])
+    assert keep.size == n_grid and n_sg == 63 + 35
+    w, rhs = _weights_rhs(Sg)
+    ran = []
+    fs = FitSystem(Sg['G_data'], Sg['Gc'], keep, Sg['Gc'].col_N, grids=Sg['grids'], sensor_grids=Sf['sensor_grids'])
+    try:
+        for precond in (1, 3, 4):
+            ok, why = fs.solver.cg_available(precond)
+            assert ok, (precond, why)
+            x = fs.solve(w, np.ones(fs.n_data, bool), rhs, precond=precond, method=1, maxit=200000, **TOL)
+            a = fs.sg_vals.copy()          # lsq_get_sensor_grids plus the magnitude prior of grid 2
+            assert np.array_equal(a[:63], fs.solver.sensor_grids()[:63])
+            assert np.array_equal(a[63:], fs.solver.sensor_grids()[63:] + 0.25)
+            ran.append(precond)
+            assert fs.stats['method'] == 1 and fs.stats['istop'] in (1, 2), (precond, fs.stats)
+            eg = np.linalg.norm(x - xs[:n_grid]) / np.linalg.norm(xs[:n_grid])
+            ea = np.linalg.norm(a - xs[n_grid:]) / np.linalg.norm(xs[n_grid:])
+            print(f'precond {precond}: {fs.stats["iters"]} iterations, grid unknowns {eg:.2e}, sensor grids {ea:.2e}')
+            assert eg <= REL and np.max(np.abs(x - xs[:n_grid])) <= ABS, (precond, eg)
+            assert ea <= REL and np.max(np.abs(a - xs[n_grid:])) <= ABS, (precond, ea)
+            assert np.array_equal(fs.expand(x)[fs.n_full:], a)
+    finally:
+        fs.close()
+    assert ran == [1, 3, 4], ran
+
+
+def test_warm_start_after_a_mask_change(gpu_available):
+    S, fs, w, rhs = _synthetic_system('t64')
+    rng = np.random.default_rng(36)
+    keep1 = rng.random(fs.n_data) > 0.1
+    keep2 = keep1 & (rng.random(fs.n_data) > 0.05)
+    layout = _layouts(fs.n_data, keep1, rng)['sizes']
+    w2 = w * np.where(np.arange(w.size) < fs.n_data, rng.uniform(0.5, 2, w.size), 1.0)
+    try:
+        fs.solver.set_sensor_grids(*layout)
+        x1 = fs.solve(w2, keep1, rhs, precond=3, method=1, **TOL)
+        xw = fs.solve(w2, keep2, rhs, x0=x1, precond=3, method=1, **TOL)
+        aw, it_warm = fs.solver.sensor_grids(), fs.stats['iters']
+        xc = fs.solve(w2, keep2, rhs, precond=3, method=1, **TOL)
+        ac, it_cold = fs.solver.sensor_grids(), fs.stats['iters']
+        xj = fs.solve(w2, keep2, rhs, x0=x1, precond=1, method=1, **TOL)
+    finally:
+        fs.close()
+    assert np.linalg.norm(xw - xc) / np.linalg.norm(xc) <= 1e-8
+    assert np.linalg.norm(xj - xc) / np.linalg.norm(xc) <= 1e-8
+    assert np.linalg.norm(aw - ac) / np.linalg.norm(ac) <= 1e-8
+    assert it_warm < it_cold
+
+
+def _rel(a, b):
+    a, b = np.asarray(a, float), np.asarray(b, float)
+    ok = np.isfinite(b)
+    return np.linalg.norm(a[ok] - b[ok]) / max(np.linalg.norm(b[ok]), 1e-300)
+
+
+@pytest.mark.parametrize('mode', ['eliminate', 'columns', 'auto'])
+def test_smooth_fit_with_sensor_grids_matches_reference(gpu_available, mode):
+    g = golden('sys_sgrid.npz')
+    kw = golden_kwargs(g)
+    # 'auto' eliminates above lsq_dense_max grid unknowns; at the default the small fit takes 'columns'
+    extra = dict(lsq_bias=mode, lsq_dense_max=0) if mode != 'columns' else dict(lsq_bias='columns')
+    S = LS.smooth_fit(data=golden_points(g), **kw, **extra)
+    d, m = S['data'], S['m']
+    assert int(np.sum(d.three_sigma_edit != g['data_three_sigma_edit'].astype(bool))) == 0
+    assert _rel(d.sigma_extra, g['data_sigma_extra']) < 1e-5
+    assert _rel(m['z0'].z0, g['z0']) < 1e-6
+    assert _rel(m['dz'].dz, g['dz']) < 1e-6
+    assert _rel(d.z_est, g['data_z_est']) < 1e-6
+    assert m['all'].size == g['m_all'].size and _rel(m['all'], g['m_all']) < 1e-6
+    assert list(m['sensor_bias_grids']) == NAMES
+    for k, name in enumerate(NAMES):
+        sg = m['sensor_bias_grids'][name]
+        assert np.array_equal(sg.x, g[f'sgrid{k}_x']) and np.array_equal(sg.y, g[f'sgrid{k}_y'])
+        assert sg.z.shape == g[f'sgrid{k}_z'].shape and _rel(sg.z, g[f'sgrid{k}_z']) < 1e-6
+        assert tuple(S['grids'][name].shape) == sg.z.shape
+    n_sg = sum(g[f'sgrid{k}_z'].size for k in range(2))
+    assert np.array_equal(m['all'][-n_sg:], np.concatenate([m['sensor_bias_grids'][n].z.ravel() for n in NAMES]))
+    assert S['timing']['sensor_grids'] == ('columns' if mode == 'columns' else 'eliminate')
+    assert S['timing']['lsq_last']['method'] == (0 if mode == 'columns' else 1)
+    assert S['timing']['formation'] == ('coo' if mode == 'columns' else 'stencil')
+
+
+def test_auto_takes_columns_for_a_small_fit_and_beside_biases(gpu_available):
+    g = golden('sys_sgrid.npz')
+    kw = golden_kwargs(g)
+    Sa = LS.smooth_fit(data=golden_points(g), lsq_bias='auto', **kw)       # ≤ lsq_dense_max grid unknowns
+    assert Sa['timing']['sensor_grids'] == 'columns' and Sa['timing']['formation'] == 'coo'
+    assert _rel(Sa['m']['all'], g['m_all']) < 1e-6
+    D = golden_points(g)
+    D.assign(sigma_corr=np.full(D.size, 0.5))
+    with pytest.warns(RuntimeWarning, match="takes 'columns'"):
+        Sb = LS.smooth_fit(data=D, lsq_bias='auto', bias_params=['sensor'], **kw)
+    assert Sb['timing']['sensor_grids'] == 'columns' and list(Sb['m']['sensor_bias_grids']) == NAMES
