@@ -469,7 +469,8 @@ int lsq_profile_kernels(lsq_handle* h, int32_t reps, int32_t op, double* out8);
  * preconditioner (it builds the normal-stencil tables), 0 when it would fall back to LSQR (the
  * reason is in lsq_last_error).  lsq_profile_cg: per-kernel HIP-event times of one CG iteration,
  * out8 = {ms data rows t = Ad·p, ms normal operator q = N p + Adᵀt, ms update + preconditioner,
- * ms of the two scalar kernels, algorithmic HBM bytes per launch of the first three, 0}.
+ * ms of the two scalar kernels, algorithmic HBM bytes per launch of the first three, mode bits:
+ * 1 matrix-free data rows, 2 wave-strip normal kernel, 4 column-mode operator (else tile mode)}.
  * lsq_normal_apply: q = AᵀA p for the current row weights/mask, p and q over the FULL column
  * space (length n_full of lsq_set_col_map; test hook for the normal operator). */
 int lsq_cg_available(lsq_handle* h, int32_t precond);

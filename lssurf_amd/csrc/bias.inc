@@ -274,11 +274,15 @@ void slope_launch_group(const System& S, const CgState* st, int mode, double* pa
 }
 
 // sD = β per rank for the sums of src: (Σ_{i∈j} src_i) / D_j, and with slopes γ per group and
-// β_j = (s_j − e_j·γ) / D_j.  part (nullable): B.nbk partials of −(Σ_j s_j β_j + Σ_s h_s·γ_s)
-void bias_launch_reduce(const System& S, const CgState* st, const double* src, double* part) {
+// β_j = (s_j − e_j·γ) / D_j.  part (nullable): B.nbk partials of −(Σ_j s_j β_j + Σ_s h_s·γ_s).
+// marks (nullable): the step's stages E0 (chunk pass), E1 (per-rank sums), E2 (per-group kernel)
+void bias_launch_reduce(const System& S, const CgState* st, const double* src, double* part, CgMarks* marks = nullptr) {
     bias_launch_chunks(S, st, src);
+    cg_mark(marks, CG_E0, S.stream);
     bias_launch_seg(S, st, 1, part);
+    cg_mark(marks, CG_E1, S.stream);
     if (S.bias.ng) slope_launch_group(S, st, 2, part ? part + S.bias.nrk : nullptr);
+    cg_mark(marks, CG_E2, S.stream);
 }
 
 // mode 0: td −= W² Z [β; γ]; mode 1: td = −W² Z [β; γ] (after bias_launch_reduce)
@@ -291,12 +295,6 @@ void bias_launch_apply(const System& S, const CgState* st, double* td, int mode)
     else
         hipLaunchKernelGGL(k_bias_apply, dim3(grid_for(B.npts)), dim3(BLOCK), 0, S.stream, st, B.npts, B.rank_pt.p,
                            B.w2.p, B.sD.p, td, mode);
-}
-
-// the elimination step on td (W² A_d p per sorted point): td ← W (I − Q) W A_d p, part as above
-void bias_launch_step(const System& S, const CgState* st, double* td, double* part) {
-    bias_launch_reduce(S, st, td, part);
-    bias_launch_apply(S, st, td, 0);
 }
 
 // per solve (beside k_dmf_rs): w² per sorted point and D_j = Σ w² + c_j² for the current weights / mask;

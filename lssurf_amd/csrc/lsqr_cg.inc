@@ -21,6 +21,13 @@
 // Preconditioners: M = blockdiag(R_bᵀR_b) = the (y, x)-node blocks of AᵀA (precond 3), or
 // diag(AᵀA) (precond 1).  In exact arithmetic the iterates equal LSQR's on A·M^{-1/2} (same
 // Krylov space, same minimised residual), so "iterations" count the same unit of progress.
+//
+// Where to add a term to the operator: cg_launch_apply (q = N p, the stages of enum CgStage) and
+// cg_launch_update (α, update, β) spell the plain step once.  The profilers (cg_profile_steps), the
+// test hook cg_apply_normal and the ranks of a group (group_cg_iteration) all run it; only
+// cg_launch_iteration's two tuned column-mode branches spell their own overlapped order from the
+// same helpers.  The multigrid's level-0 operator (mg.inc, mg_launch_op) carries no elimination on
+// purpose and is separate.
 
 namespace {
 
@@ -372,134 +379,6 @@ __global__ __launch_bounds__(BLOCK) void k_cg_dmf_atq(const CgState* st, DmfDesc
                 qc[e] = qv[k] + L[(e - nl * S2) * 64 + nl];
             }
         }
-    }
-}
-
-// The same q += Adᵀ td, streamed down node rows (round 4): a wave owns 64 node columns (lane = node)
-// and a chunk of RY node rows, and walks the CELL rows cy = ya − 1 … yb − 1 once.  A point of cell
-// row cy feeds node row cy (weight 1 − f_y) and node row cy + 1 (f_y), so each cell row's points
-// are read once per lane instead of twice (k_cg_dmf_atq reads the two cell rows of every node row),
-// and the next cell row's run starts and the next node row's q are loaded while the current one is
-// summed.  Two accumulator sets in LDS ([t][lane] as k_cg_dmf_atq): node row cy (complete after this
-// cell row: flushed) and node row cy + 1 (carried).  Every node sums its points in k_cg_dmf_atq's
-// order (cell row y − 1, then y; sorted order within), with the same products: q is bitwise the same.
-constexpr int DMF_RY = 8;   // node rows per wave (the chunk's first cell row is shared with the chunk above)
-template <int MT>
-__global__ __launch_bounds__(BLOCK) void k_cg_dmf_atq_rw(const CgState* __restrict__ st, DmfDesc D, int ry,
-                                                         const int32_t* __restrict__ cell,
-                                                         const double4* __restrict__ pt,
-                                                         const double* __restrict__ td, double* __restrict__ q) {
-    if (st->stop) return;
-    __shared__ double LA[BLOCK / 64][2][MT * 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int nsx = (D.S1 + 63) / 64, C1 = D.S1 - 1, S2 = D.S2;
-    const int nch = (D.S0 + ry - 1) / ry;
-    const int64_t job = (int64_t)xcd_block(blockIdx.x, gridDim.x) * (BLOCK / 64) + w;   // grid: a multiple of 8
-    if (job >= (int64_t)nsx * nch) return;
-    const int ch = (int)(job / nsx), xs = (int)(job - (int64_t)ch * nsx);
-    const int x0 = xs * 64, nv = min(64, D.S1 - x0);
-    const int ya = ch * ry, yb = min(D.S0, ya + ry);
-    const int ix = x0 + lane;
-    const bool mine = ix < D.S1;
-    const int cxl = max(ix - 1, 0), cxh = min(ix, C1 - 1);
-    double* A = LA[w][0];   // node row cy (receives cell row cy's lower corners, then flushed)
-    double* B = LA[w][1];   // node row cy + 1 (upper corners; carried to the next step)
-#pragma unroll
-    for (int k = 0; k < MT; ++k) {
-        A[k * 64 + lane] = 0.0;
-        B[k * 64 + lane] = 0.0;
-    }
-    double za = 0.0, zb = 0.0;   // the 2-D (z0) parts' sums of the same two node rows
-    const int c0 = max(ya - 1, 0), c1 = min(yb, D.S0 - 1);   // cell rows
-    // the first cell row's point run
-    int pa = 0, pb = 0;
-    if (mine && c0 < c1) {
-        pa = cell[c0 * C1 + cxl];
-        pb = cell[c0 * C1 + cxh + 1];
-    }
-    for (int cy = c0; cy <= c1; ++cy) {
-        // node row cy is complete after this step when cy < S0 − 1 (cell row cy exists); the last
-        // node row (cy = S0 − 1) only has cell row S0 − 2, already carried
-        const bool has_cells = cy < c1;
-        const bool flush = cy >= ya && cy < yb;
-        int na = 0, nb = 0;   // the next cell row's run, in flight while this one is summed
-        if (mine && cy + 1 < c1) {
-            na = cell[(cy + 1) * C1 + cxl];
-            nb = cell[(cy + 1) * C1 + cxh + 1];
-        }
-        double qv[MT], q2[2];
-        double* __restrict__ qc = q + D.col3 + ((int64_t)cy * D.S1 + x0) * S2;
-        const int64_t nd = (int64_t)cy * D.S1 + ix;
-        if (flush) {   // this node row's q, loaded before its sums
-            if (D.n3) {
-#pragma unroll
-                for (int k = 0; k < MT; ++k) qv[k] = lane + 64 * k < nv * S2 ? qc[lane + 64 * k] : 0.0;
-            }
-#pragma unroll
-            for (int k = 0; k < 2; ++k) q2[k] = mine && k < D.n2 ? q[D.col2[k] + nd] : 0.0;
-        }
-        if (mine && has_cells) {
-            const int ntot = pb - pa;
-            for (int j0 = 0; j0 < ntot; j0 += DMF_U) {
-                double4 P[DMF_U];
-                double tj[DMF_U];
-#pragma unroll
-                for (int u = 0; u < DMF_U; ++u) {
-                    const bool in = j0 + u < ntot;
-                    P[u] = in ? pt[pa + j0 + u] : make_double4(0.0, 0.0, 0.0, 0.0);
-                    tj[u] = in ? td[pa + j0 + u] : 0.0;   // past the run: 0·w
-                }
-#pragma unroll
-                for (int u = 0; u < DMF_U; ++u) {
-                    double fy, fx;
-                    (void)dmf_cell(P[u].x, D.S0, fy);
-                    const int pcx = dmf_cell(P[u].y, D.S1, fx);
-                    const double wx = pcx == ix ? 1.0 - fx : fx;
-                    const double wlo = (1.0 - fy) * wx, whi = fy * wx;   // node rows cy, cy + 1
-                    za += wlo * tj[u];
-                    zb += whi * tj[u];
-                    if (D.n3) {
-                        double ft;
-                        const int ct = dmf_cell(P[u].z, D.S2, ft);
-                        A[ct * 64 + lane] += (wlo * (1.0 - ft)) * tj[u];
-                        A[(ct + 1) * 64 + lane] += (wlo * ft) * tj[u];
-                        B[ct * 64 + lane] += (whi * (1.0 - ft)) * tj[u];
-                        B[(ct + 1) * 64 + lane] += (whi * ft) * tj[u];
-                    }
-                }
-            }
-        }
-        if (flush) {
-#pragma unroll
-            for (int k = 0; k < 2; ++k)
-                if (mine && k < D.n2) q[D.col2[k] + nd] = q2[k] + za;
-            if (D.n3) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();   // one wave's LDS operations are ordered: the other lanes' columns
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-                for (int k = 0; k < MT; ++k) {
-                    const int e = lane + 64 * k;
-                    if (e < nv * S2) {
-                        const int nl = e / S2;
-                        qc[e] = qv[k] + A[(e - nl * S2) * 64 + nl];
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            }
-        }
-        // rotate: B (node row cy + 1) becomes the next step's A; the old A is cleared for reuse
-#pragma unroll
-        for (int k = 0; k < MT; ++k) A[k * 64 + lane] = 0.0;
-        double* t_ = A;
-        A = B;
-        B = t_;
-        za = zb;
-        zb = 0.0;
-        pa = na;
-        pb = nb;
     }
 }
 
@@ -2099,6 +1978,29 @@ void cg_launch_precond(System& S, const CgGrids& g, int precond) {
 // before the normal kernel), column mode reads the p the normal kernel wrote
 bool cg_use_dmf(const System& S) { return S.cgh.colmode && S.dmf.ok; }
 
+// ---- the plain step's stages, in column mode's launch order (DESIGN.md §CGNR, "The step's stages") --
+// q = N p (cg_launch_apply): NORMAL, AD, the elimination's E0 … E3 (elim_nbk), XR_FWD and XR_ATQ
+// (xr_active), ATQ; tile mode runs AD, then NORMAL (which adds ATd·t), and nothing else.  Then
+// cg_launch_update: ALPHA, PRECOND, BETA.  BEGIN stands before the step's first launch.
+enum CgStage {
+    CG_BEGIN, CG_NORMAL, CG_AD, CG_E0, CG_E1, CG_E2, CG_E3, CG_XR_FWD, CG_XR_ATQ, CG_ATQ, CG_ALPHA, CG_PRECOND,
+    CG_BETA, CG_NSTAGE
+};
+constexpr unsigned cg_bit(int stage) { return 1u << stage; }
+
+// The profilers' stage marks: an event behind every stage of mask, in launch order (ev holds enough
+// for every repetition; stage names the ones recorded so far).  The solver passes no marks.
+struct CgMarks {
+    unsigned mask = 0;
+    std::vector<hipEvent_t> ev;
+    std::vector<int> stage;
+};
+inline void cg_mark(CgMarks* m, int stage, hipStream_t st) {
+    if (!m || !(m->mask & cg_bit(stage))) return;
+    HIP_CHECK(hipEventRecord(m->ev[m->stage.size()], st));
+    m->stage.push_back(stage);
+}
+
 #include "bias.inc"
 #include "sgrid.inc"
 #include "xrows.inc"
@@ -2121,28 +2023,32 @@ int cg_nt(const System& S, const CgGrids& g) {
 
 // extra rows set: t_x = W_x X p and q += Xᵀ W_x t_x, after q = N_s p (and its x-edge correction) and
 // before the node gather whose workgroup 0 sums the partials (xrows.inc)
-void cg_launch_xr(System& S, const CgGrids& g, const double* pnew) {
+void cg_launch_xr(System& S, const CgGrids& g, const double* pnew, CgMarks* marks = nullptr) {
     if (!xr_active(S)) return;
     xr_launch_fwd(S, S.cst.p, nullptr, pnew, 1.0, S.cg_part_t.p + g.gD + elim_nbk(S));
+    cg_mark(marks, CG_XR_FWD, S.stream);
     xr_launch_atq(S, S.cst.p, S.cg_q.p);
+    cg_mark(marks, CG_XR_ATQ, S.stream);
 }
 
 // biases or sensor grids set: td ← W(I − Q)W A_d p between Ad·p and q += Adᵀ td (bias.inc, sgrid.inc)
-void cg_launch_bias(System& S, const CgGrids& g) {
-    if (elim_nbk(S)) elim_launch_step(S, S.cst.p, S.cg_t.p, S.cg_part_t.p + g.gD);
+void cg_launch_bias(System& S, const CgGrids& g, CgMarks* marks = nullptr) {
+    if (elim_nbk(S)) elim_launch_step(S, S.cst.p, S.cg_t.p, S.cg_part_t.p + g.gD, marks);
 }
 
-void cg_launch_data(System& S, const CgGrids& g, const double* pold, const double* pnew) {
-    if (cg_use_dmf(S)) {
+// t = Ad·p and its elimination (elim_nbk needs the matrix-free data rows)
+void cg_launch_data(System& S, const CgGrids& g, const double* pold, const double* pnew, CgMarks* marks = nullptr) {
+    if (cg_use_dmf(S))
         hipLaunchKernelGGL(k_cg_dmf_ad, dim3(g.gD), dim3(BLOCK), 0, S.stream, S.cst.p, S.dmf,
                            reinterpret_cast<const double4*>(S.dmf_pt.p), pnew, S.cg_t.p, S.cg_part_t.p);
-        cg_launch_bias(S, g);
-    } else if (S.cgh.colmode)
+    else if (S.cgh.colmode)
         hipLaunchKernelGGL(k_cg_data, dim3(g.gD), dim3(BLOCK), 0, S.stream, S.cst.p, S.mfh.npts, S.Ad.nslices,
                            S.Ad.sp.p, S.Ad.ci.p, S.Ad.val.p, pnew, nullptr, S.cg_t.p, S.cg_part_t.p);
     else
         hipLaunchKernelGGL(k_cg_data, dim3(g.gD), dim3(BLOCK), 0, S.stream, S.cst.p, S.mfh.npts, S.Ad.nslices,
                            S.Ad.sp.p, S.Ad.ci.p, S.Ad.val.p, S.cg_z.p, pold, S.cg_t.p, nullptr);
+    cg_mark(marks, CG_AD, S.stream);
+    cg_launch_bias(S, g, marks);
 }
 
 // k_cg_dmf_atq: 4 strips of 64 nodes per workgroup, the grid a multiple of 8 (xcd_block)
@@ -2151,23 +2057,12 @@ dim3 cg_atq_grid(const System& S) {
     return dim3((unsigned)(((strips + BLOCK / 64 - 1) / (BLOCK / 64) + 7) / 8 * 8));
 }
 
-// q += Adᵀ td by node (matrix-free data rows): the per-node kernel k_cg_dmf_atq, or with
-// LSQ_CG_ATQ_RW=1 the row-streaming k_cg_dmf_atq_rw (S2 ≤ 12; same q bit for bit — the parity
-// test toggles it per launch).  Measured at C4: the row-streaming kernel with 8 node rows per wave
-// 4–12 µs SLOWER per application (2 048 waves for 1 024 SIMDs: each wave's 9 dependent cell-row
-// steps are not hidden), so it is not the default; LSQ_CG_ATQ_RY sets its rows per wave.
+// q += Adᵀ td by node (matrix-free data rows); ast set: α from the partials in workgroup 0 (the
+// production step).  Streaming the cell rows per wave instead measured slower (DESIGN.md §3, multigrid:
+// "measured and dropped")
 void cg_launch_dmf_atq(const System& S, const CgState* st, const double* td, double* q, CgState* ast = nullptr,
                        const double* apg = nullptr, int ang = 0, const double* apt = nullptr, int ant = 0) {
     const double4* P = reinterpret_cast<const double4*>(S.dmf_pt.p);
-    const char* e = getenv("LSQ_CG_ATQ_RW");
-    if (S.dmf.S2 <= 12 && e && e[0] == '1') {
-        const char* er = getenv("LSQ_CG_ATQ_RY");
-        const int ry = er ? std::max(1, atoi(er)) : DMF_RY;
-        const int64_t jobs = (int64_t)((S.dmf.S1 + 63) / 64) * ((S.dmf.S0 + ry - 1) / ry);
-        const dim3 grid((unsigned)(((jobs + BLOCK / 64 - 1) / (BLOCK / 64) + 7) / 8 * 8));
-        hipLaunchKernelGGL(k_cg_dmf_atq_rw<12>, grid, dim3(BLOCK), 0, S.stream, st, S.dmf, ry, S.dmf_cell.p, P, td, q);
-        return;
-    }
     const dim3 grid = cg_atq_grid(S);
     if (S.dmf.S2 <= 12)
         hipLaunchKernelGGL(k_cg_dmf_atq<12>, grid, dim3(BLOCK), 0, S.stream, st, S.dmf, S.dmf_cell.p, P, td, q, ast, apg,
@@ -2213,39 +2108,79 @@ void cg_launch_normal(System& S, const CgGrids& g, const double* pold, double* p
     }
 }
 
+// the normal stencil's partials of pᵀNp (with the x-edge correction's and the field-valued parts')
+int cg_ng(const System& S, const CgGrids& g) { return g.gN + (S.cgh.colmode ? S.cgh.nedge : 0) + S.cg_nvb; }
+
 void cg_launch_alpha(System& S, const CgGrids& g) {
-    hipLaunchKernelGGL(k_cg_alpha, dim3(1), dim3(BLOCK), 0, S.stream, S.cst.p, S.cg_part_g.p,
-                       g.gN + (S.cgh.colmode ? S.cgh.nedge : 0) + S.cg_nvb, S.cg_part_t.p, cg_nt(S, g),
+    hipLaunchKernelGGL(k_cg_alpha, dim3(1), dim3(BLOCK), 0, S.stream, S.cst.p, S.cg_part_g.p, cg_ng(S, g),
+                       S.cg_part_t.p, cg_nt(S, g), S.dist ? S.gsum.p : nullptr);
+}
+
+// mode 1: ρ0 of the start; mode 0: the step's β.  A rank of a group reads the all-reduced sᵀz
+void cg_launch_beta(System& S, const CgGrids& g, int mode) {
+    hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(BLOCK), 0, S.stream, S.cst.p, S.cg_part_r.p, g.gB, mode,
                        S.dist ? S.gsum.p : nullptr);
 }
 
+// everything of q = N p behind the normal stencil: t = Ad·p with its elimination, the extra rows,
+// q += Adᵀ t.  Tile mode: t alone, k_cg_normal adds ATd·t
+void cg_launch_rows(System& S, const CgGrids& g, const double* pold, const double* pnew, CgMarks* marks = nullptr) {
+    cg_launch_data(S, g, pold, pnew, marks);
+    if (!S.cgh.colmode) return;
+    cg_launch_xr(S, g, pnew, marks);
+    cg_launch_atdq(S);
+    cg_mark(marks, CG_ATQ, S.stream);
+}
+
+// THE plain step, first half: p = z + β p_old and q = N p with every partial of pᵀNp, each stage in
+// the order the mode requires.  A term added to the operator is added here (and to the two tuned
+// spellings in cg_launch_iteration); the profilers, the test hook and the ranks of a group follow.
+void cg_launch_apply(System& S, const CgGrids& g, const double* pold, double* pnew, CgMarks* marks = nullptr) {
+    cg_mark(marks, CG_BEGIN, S.stream);
+    if (S.cgh.colmode) {   // normal (writes p, q = N_s p) → data (t = Ad p) → q += ATd·t
+        cg_launch_normal(S, g, pold, pnew);
+        cg_mark(marks, CG_NORMAL, S.stream);
+        cg_launch_rows(S, g, pold, pnew, marks);
+    } else {               // data → normal (adds ATd·t)
+        cg_launch_rows(S, g, pold, pnew, marks);
+        cg_launch_normal(S, g, pold, pnew);
+        cg_mark(marks, CG_NORMAL, S.stream);
+    }
+}
+
+// the plain step, second half: α, the preconditioned update, β
+void cg_launch_update(System& S, const CgGrids& g, int precond, CgMarks* marks = nullptr) {
+    cg_launch_alpha(S, g);
+    cg_mark(marks, CG_ALPHA, S.stream);
+    cg_launch_precond(S, g, precond);
+    cg_mark(marks, CG_PRECOND, S.stream);
+    cg_launch_beta(S, g, 0);
+    cg_mark(marks, CG_BETA, S.stream);
+}
+
 // one CG iteration of phase ph (0 … CG_XK − 1): p_old in the previous phase's buffer, p_new to
-// phase ph's.  Tile mode: data → normal (adds ATd·t); column mode: normal (writes p, q = N_s p) →
-// data (t = Ad p) → q += ATd·t
+// phase ph's.  Two tuned, overlapped spellings of the column-mode step, else the plain one.  Single
+// systems only: a group's ranks step through group_cg_iteration (lsq_solve and lsq_iterate branch
+// on S.dist before they reach cg_solve / cg_iterate).
 void cg_launch_iteration(System& S, const CgGrids& g, int ph, int precond) {
     const double* pold = cg_pold(S, ph);
     double* pnew = cg_pnew(S, ph);
     if (cg_use_dmf(S) && S.cg_var.empty() && S.cgh.pad[1] == 8) {
         // the x-edge correction (q at the dim-1 edge nodes, latency-bound) in the data rows'
-        // Ad·p launch (both read p only), then q += Adᵀt
+        // Ad·p launch (both read p only), then q += Adᵀt with α in the node gather's workgroup 0
         cg_launch_normal(S, g, pold, pnew, false);
         hipLaunchKernelGGL(k_cg_ad_xedge<8>, dim3(g.gD + S.cgh.nedge), dim3(BLOCK), 0, S.stream, S.cst.p, S.dmf,
                            reinterpret_cast<const double4*>(S.dmf_pt.p), pnew, S.cg_t.p, S.cg_part_t.p, g.gD, S.cgd.p,
                            S.cg_coef.p, S.cg_q.p, S.cg_part_g.p + g.gN);
         cg_launch_bias(S, g);
         cg_launch_xr(S, g, pnew);
-        // α in the node gather's workgroup 0 (LSQ_CG_FUSE_ALPHA=0: its own launch)
-        static const bool fuse_env = !getenv("LSQ_CG_FUSE_ALPHA") || atoi(getenv("LSQ_CG_FUSE_ALPHA")) != 0;
-        const char* rw = getenv("LSQ_CG_ATQ_RW");
-        if (fuse_env && !S.dist && !(rw && rw[0] == '1')) {
-            cg_launch_dmf_atq(S, S.cst.p, S.cg_t.p, S.cg_q.p, S.cst.p, S.cg_part_g.p,
-                              g.gN + (S.cgh.colmode ? S.cgh.nedge : 0) + S.cg_nvb, S.cg_part_t.p, cg_nt(S, g));
-            cg_launch_precond(S, g, precond);
-            hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(BLOCK), 0, S.stream, S.cst.p, S.cg_part_r.p, g.gB, 0, nullptr);
-            return;
-        }
-        cg_launch_atdq(S);
-    } else if (S.cgh.colmode) {
+        cg_launch_dmf_atq(S, S.cst.p, S.cg_t.p, S.cg_q.p, S.cst.p, S.cg_part_g.p, cg_ng(S, g), S.cg_part_t.p,
+                          cg_nt(S, g));
+        cg_launch_precond(S, g, precond);
+        cg_launch_beta(S, g, 0);
+        return;
+    }
+    if (S.cgh.colmode) {
         // the x-edge correction (q at the dim-1 edge nodes, latency-bound) runs beside the data
         // rows' Ad·p, which reads p only; both join before q += Adᵀt
         cg_launch_normal(S, g, pold, pnew, false);
@@ -2259,12 +2194,9 @@ void cg_launch_iteration(System& S, const CgGrids& g, int ph, int precond) {
         cg_launch_xr(S, g, pnew);   // after the join: the x-edge pass on S.side also updates q
         cg_launch_atdq(S);
     } else {
-        cg_launch_data(S, g, pold, pnew);
-        cg_launch_normal(S, g, pold, pnew);
+        cg_launch_apply(S, g, pold, pnew);
     }
-    cg_launch_alpha(S, g);
-    cg_launch_precond(S, g, precond);
-    hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(BLOCK), 0, S.stream, S.cst.p, S.cg_part_r.p, g.gB, 0, nullptr);
+    cg_launch_update(S, g, precond);
 }
 
 // s0 = Aᵀ(W b − A x0), z0 = M⁻¹ s0, ρ0 (x0 = warm start in compact columns, or null)
@@ -2380,7 +2312,7 @@ void cg_init(System& S, const double* h_b, const double* h_x0, const lsq_opts& o
         tr.mark(st, "mg_setup");
     }
     cg_launch_precond(S, g, precond);   // α = 0, p = q = 0, pend = 0: z0 = M⁻¹ s0 and ρ0
-    hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(BLOCK), 0, st, S.cst.p, S.cg_part_r.p, g.gB, 1, nullptr);
+    cg_launch_beta(S, g, 1);
     KERNEL_CHECK();
     HIP_CHECK(hipStreamSynchronize(st));
     tr.mark(st, "z0 = M^-1 s0");
@@ -2575,51 +2507,62 @@ int cg_iterate(System& S, const double* h_b, int64_t iters, const lsq_opts& o, l
     return 0;
 }
 
-// Per-kernel HIP-event times of one CG iteration's launches (reps each, benign state) and the
-// algorithmic bytes per launch: out8 = {ms data, ms normal, ms precond, ms scalars (α + β),
-// bytes data, bytes normal, bytes precond, 0}.  Clobbers the iteration state.
+static bool cg_live(const System& S, int precond) { return S.cg_ready && S.cg_mode == precond; }
+
+static void cg_need_live(const System& S, int precond, const char* who) {
+    if (!cg_live(S, precond))
+        throw std::invalid_argument(std::string(who) + ": needs the live state of lsq_iterate with this precond");
+}
+
+// The profilers' core: reps real steps of a live lsq_iterate state (no stop) through the plain step,
+// an event behind every stage of mask, so every kernel sees the caches its predecessors leave
+// behind.  ms[s] = the mean time from the step's previous mark to the one behind stage s (0 for a
+// stage that is not in mask, did not run, or carries the step's first mark).
+static void cg_profile_steps(System& S, int reps, int precond, unsigned mask, double ms[CG_NSTAGE]) {
+    const CgGrids g = cg_grids(S, precond);
+    CgMarks m;
+    m.mask = mask;
+    m.ev.resize((size_t)reps * __builtin_popcount(mask));
+    for (auto& e : m.ev) HIP_CHECK(hipEventCreate(&e));
+    for (int r = 0; r < reps; ++r) {
+        cg_launch_apply(S, g, cg_pold(S, S.cg_parity), cg_pnew(S, S.cg_parity), &m);
+        cg_launch_update(S, g, precond, &m);
+        S.cg_parity = (S.cg_parity + 1) % CG_XK;
+    }
+    HIP_CHECK(hipStreamSynchronize(S.stream));
+    std::fill(ms, ms + CG_NSTAGE, 0.0);
+    const size_t per = m.stage.size() / reps;   // every step records the same marks
+    for (size_t i = 0; i < m.stage.size(); ++i) {
+        if (i % per == 0) continue;
+        float a = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&a, m.ev[i - 1], m.ev[i]));
+        ms[m.stage[i]] += a;
+    }
+    for (auto& e : m.ev) (void)hipEventDestroy(e);
+    for (int s = 0; s < CG_NSTAGE; ++s) ms[s] /= reps;
+}
+
+// Per-kernel HIP-event times of one CG iteration's launches and the algorithmic bytes per launch:
+// out8 = {ms data, ms normal, ms precond, ms scalars (α + β), bytes data, bytes normal, bytes
+// precond, mode bits}.  On a live lsq_iterate state: inside reps real iterations; else reps
+// launches of each role on a benign state, which clobbers the iteration state.
 void cg_profile(System& S, int reps, int precond, double* out) {
     const CgGrids g = cg_grids(S, precond);
-    if (S.cg_ready && S.cg_mode == precond) {
-        // a live lsq_iterate state (no stop): time each role inside real iterations, events
-        // between the launches, so every kernel sees the caches its predecessors leave behind
-        std::vector<hipEvent_t> ev(6 * reps);
-        for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
-        for (int r = 0; r < reps; ++r) {
-            const int par = S.cg_parity;
-            const double* pold = cg_pold(S, par);
-            double* pnew = cg_pnew(S, par);
-            hipEvent_t* e = ev.data() + 6 * r;
-            HIP_CHECK(hipEventRecord(e[0], S.stream));
-            cg_launch_normal(S, g, pold, pnew);
-            HIP_CHECK(hipEventRecord(e[1], S.stream));
-            cg_launch_data(S, g, pold, pnew);
-            cg_launch_xr(S, g, pnew);
-            cg_launch_atdq(S);
-            HIP_CHECK(hipEventRecord(e[2], S.stream));
-            cg_launch_alpha(S, g);
-            HIP_CHECK(hipEventRecord(e[3], S.stream));
-            cg_launch_precond(S, g, precond);
-            HIP_CHECK(hipEventRecord(e[4], S.stream));
-            hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(BLOCK), 0, S.stream, S.cst.p, S.cg_part_r.p, g.gB, 0, nullptr);
-            HIP_CHECK(hipEventRecord(e[5], S.stream));
-            S.cg_parity = (S.cg_parity + 1) % CG_XK;
-        }
-        HIP_CHECK(hipEventSynchronize(ev.back()));
-        double t[4] = {0, 0, 0, 0};   // data, normal, update, scalars
-        for (int r = 0; r < reps; ++r) {
-            float a = 0.f;
-            hipEvent_t* e = ev.data() + 6 * r;
-            HIP_CHECK(hipEventElapsedTime(&a, e[0], e[1])); t[1] += a;
-            HIP_CHECK(hipEventElapsedTime(&a, e[1], e[2])); t[0] += a;
-            HIP_CHECK(hipEventElapsedTime(&a, e[2], e[3])); t[3] += a;
-            HIP_CHECK(hipEventElapsedTime(&a, e[3], e[4])); t[2] += a;
-            HIP_CHECK(hipEventElapsedTime(&a, e[4], e[5])); t[3] += a;
-        }
-        for (auto& e : ev) (void)hipEventDestroy(e);
-        for (int k = 0; k < 4; ++k) out[k] = t[k] / reps;
-        out[7] = (cg_use_dmf(S) ? 1.0 : 0.0) + (S.cgh.rw ? 2.0 : 0.0);
-        cg_kernel_bytes(S, precond, out + 4);
+    // bit 0: data rows matrix-free (else stored Ad / ATd); bit 1: wave-strip normal operator; bit 2:
+    // column mode (else tile mode)
+    out[7] = (cg_use_dmf(S) ? 1.0 : 0.0) + (S.cgh.rw ? 2.0 : 0.0) + (S.cgh.colmode ? 4.0 : 0.0);
+    cg_kernel_bytes(S, precond, out + 4);
+    if (cg_live(S, precond)) {
+        const int rows = S.cgh.colmode ? CG_ATQ : CG_AD;   // the last stage of the data rows' share
+        double ms[CG_NSTAGE];
+        cg_profile_steps(S, reps, precond,
+                         cg_bit(CG_BEGIN) | cg_bit(CG_NORMAL) | cg_bit(rows) | cg_bit(CG_ALPHA) | cg_bit(CG_PRECOND) |
+                             cg_bit(CG_BETA),
+                         ms);
+        out[0] = ms[rows];
+        out[1] = ms[CG_NORMAL];
+        out[2] = ms[CG_PRECOND];
+        out[3] = ms[CG_ALPHA] + ms[CG_BETA];
         return;
     }
     CgState h{};
@@ -2638,18 +2581,15 @@ void cg_profile(System& S, int reps, int precond, double* out) {
         for (int pass = 0; pass < 2; ++pass) {
             HIP_CHECK(hipEventRecord(e0, S.stream));
             for (int r = 0; r < reps; ++r) {
-                if (k == 0) {
-                    cg_launch_data(S, g, S.cg_pb[0].p, S.cg_pb[1].p);
-                    cg_launch_xr(S, g, S.cg_pb[1].p);
-                    if (S.cgh.colmode) cg_launch_atdq(S);
-                } else if (k == 1)
+                if (k == 0)
+                    cg_launch_rows(S, g, S.cg_pb[0].p, S.cg_pb[1].p);
+                else if (k == 1)
                     cg_launch_normal(S, g, S.cg_pb[0].p, S.cg_pb[1].p);
                 else if (k == 2)
                     cg_launch_precond(S, g, precond);
                 else {
                     cg_launch_alpha(S, g);
-                    hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(BLOCK), 0, S.stream, S.cst.p, S.cg_part_r.p, g.gB, 0,
-                                       nullptr);
+                    cg_launch_beta(S, g, 0);
                 }
             }
             HIP_CHECK(hipEventRecord(e1, S.stream));
@@ -2661,155 +2601,50 @@ void cg_profile(System& S, int reps, int precond, double* out) {
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    // bit 0: data rows matrix-free (else stored Ad / ATd); bit 1: wave-strip normal operator
-    out[7] = (cg_use_dmf(S) ? 1.0 : 0.0) + (S.cgh.rw ? 2.0 : 0.0);
-    cg_kernel_bytes(S, precond, out + 4);
     S.cg_ready = false;
 }
 
-// The extra rows' two kernels inside real iterations of a live lsq_iterate state (no stop), events
-// between the launches as in cg_profile, so each sees the caches the step's other kernels leave:
-// out4 = {ms k_xr_fwd, ms k_xr_atq (with k_xr_atq_long), ms of the data rows' Ad·p before them, ms of
+// The extra rows' two kernels inside real iterations (cg_profile_steps): out4 = {ms k_xr_fwd, ms
+// k_xr_atq (with k_xr_atq_long), ms of the data rows' Ad·p (with its elimination) before them, ms of
 // the node gather behind them}, means over reps iterations.
 void cg_profile_xr(System& S, int reps, int precond, double* out) {
-    if (!(S.cg_ready && S.cg_mode == precond))
-        throw std::invalid_argument("lsq_profile_extra_rows: needs the live state of lsq_iterate with this precond");
+    cg_need_live(S, precond, "lsq_profile_extra_rows");
     if (!xr_active(S)) throw std::invalid_argument("lsq_profile_extra_rows: no extra rows in the CGNR operator");
-    const CgGrids g = cg_grids(S, precond);
-    std::vector<hipEvent_t> ev(5 * reps);
-    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
-    for (int r = 0; r < reps; ++r) {
-        const int par = S.cg_parity;
-        const double* pold = cg_pold(S, par);
-        double* pnew = cg_pnew(S, par);
-        hipEvent_t* e = ev.data() + 5 * r;
-        cg_launch_normal(S, g, pold, pnew);
-        HIP_CHECK(hipEventRecord(e[0], S.stream));
-        cg_launch_data(S, g, pold, pnew);
-        HIP_CHECK(hipEventRecord(e[1], S.stream));
-        xr_launch_fwd(S, S.cst.p, nullptr, pnew, 1.0, S.cg_part_t.p + g.gD + elim_nbk(S));
-        HIP_CHECK(hipEventRecord(e[2], S.stream));
-        xr_launch_atq(S, S.cst.p, S.cg_q.p);
-        HIP_CHECK(hipEventRecord(e[3], S.stream));
-        cg_launch_atdq(S);
-        HIP_CHECK(hipEventRecord(e[4], S.stream));
-        cg_launch_alpha(S, g);
-        cg_launch_precond(S, g, precond);
-        hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(BLOCK), 0, S.stream, S.cst.p, S.cg_part_r.p, g.gB, 0, nullptr);
-        S.cg_parity = (S.cg_parity + 1) % CG_XK;
-    }
-    HIP_CHECK(hipEventSynchronize(ev.back()));
-    HIP_CHECK(hipStreamSynchronize(S.stream));
-    double t[4] = {0, 0, 0, 0};
-    for (int r = 0; r < reps; ++r) {
-        hipEvent_t* e = ev.data() + 5 * r;
-        float a = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&a, e[1], e[2])); t[0] += a;
-        HIP_CHECK(hipEventElapsedTime(&a, e[2], e[3])); t[1] += a;
-        HIP_CHECK(hipEventElapsedTime(&a, e[0], e[1])); t[2] += a;
-        HIP_CHECK(hipEventElapsedTime(&a, e[3], e[4])); t[3] += a;
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    for (int k = 0; k < 4; ++k) out[k] = t[k] / reps;
+    const int data = elim_nbk(S) ? CG_E3 : CG_AD;   // the last stage of t = Ad·p
+    double ms[CG_NSTAGE];
+    cg_profile_steps(S, reps, precond,
+                     cg_bit(CG_NORMAL) | cg_bit(data) | cg_bit(CG_XR_FWD) | cg_bit(CG_XR_ATQ) | cg_bit(CG_ATQ), ms);
+    out[0] = ms[CG_XR_FWD];
+    out[1] = ms[CG_XR_ATQ];
+    out[2] = ms[data];
+    out[3] = ms[CG_ATQ];
 }
 
-// The slope elimination's kernels inside real iterations of a live lsq_iterate state (no stop), events
-// between the launches as in cg_profile_xr: out8 = {ms chunk pass, ms per-rank sums (with the long
-// ranks), ms per-group kernel, ms apply pass, and their algorithmic bytes (slope_kernel_bytes)}, means
-// over reps iterations.
+// the elimination's four kernels inside real iterations: out4 = ms of the stages E0 … E3
+static void cg_profile_elim(System& S, int reps, int precond, double* out) {
+    double ms[CG_NSTAGE];
+    cg_profile_steps(S, reps, precond,
+                     cg_bit(CG_AD) | cg_bit(CG_E0) | cg_bit(CG_E1) | cg_bit(CG_E2) | cg_bit(CG_E3), ms);
+    std::copy(ms + CG_E0, ms + CG_E3 + 1, out);
+}
+
+// The slope elimination's kernels inside real iterations: out8 = {ms chunk pass, ms per-rank sums
+// (with the long ranks), ms per-group kernel, ms apply pass, and their algorithmic bytes
+// (slope_kernel_bytes)}, means over reps iterations.
 void cg_profile_slope(System& S, int reps, int precond, double* out) {
-    if (!(S.cg_ready && S.cg_mode == precond))
-        throw std::invalid_argument("lsq_profile_data_slope: needs the live state of lsq_iterate with this precond");
+    cg_need_live(S, precond, "lsq_profile_data_slope");
     if (!bias_active(S) || !S.bias.ng) throw std::invalid_argument("lsq_profile_data_slope: no slopes in the CGNR operator");
-    const CgGrids g = cg_grids(S, precond);
-    std::vector<hipEvent_t> ev(5 * reps);
-    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
-    for (int r = 0; r < reps; ++r) {
-        const int par = S.cg_parity;
-        const double* pold = cg_pold(S, par);
-        double* pnew = cg_pnew(S, par);
-        hipEvent_t* e = ev.data() + 5 * r;
-        double* part = S.cg_part_t.p + g.gD;
-        cg_launch_normal(S, g, pold, pnew);
-        hipLaunchKernelGGL(k_cg_dmf_ad, dim3(g.gD), dim3(BLOCK), 0, S.stream, S.cst.p, S.dmf,
-                           reinterpret_cast<const double4*>(S.dmf_pt.p), pnew, S.cg_t.p, S.cg_part_t.p);
-        HIP_CHECK(hipEventRecord(e[0], S.stream));
-        bias_launch_chunks(S, S.cst.p, S.cg_t.p);
-        HIP_CHECK(hipEventRecord(e[1], S.stream));
-        bias_launch_seg(S, S.cst.p, 1, part);
-        HIP_CHECK(hipEventRecord(e[2], S.stream));
-        slope_launch_group(S, S.cst.p, 2, part + S.bias.nrk);
-        HIP_CHECK(hipEventRecord(e[3], S.stream));
-        bias_launch_apply(S, S.cst.p, S.cg_t.p, 0);
-        HIP_CHECK(hipEventRecord(e[4], S.stream));
-        cg_launch_xr(S, g, pnew);
-        cg_launch_atdq(S);
-        cg_launch_alpha(S, g);
-        cg_launch_precond(S, g, precond);
-        hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(BLOCK), 0, S.stream, S.cst.p, S.cg_part_r.p, g.gB, 0, nullptr);
-        S.cg_parity = (S.cg_parity + 1) % CG_XK;
-    }
-    HIP_CHECK(hipStreamSynchronize(S.stream));
-    double t[4] = {0, 0, 0, 0};
-    for (int r = 0; r < reps; ++r) {
-        hipEvent_t* e = ev.data() + 5 * r;
-        for (int k = 0; k < 4; ++k) {
-            float a = 0.f;
-            HIP_CHECK(hipEventElapsedTime(&a, e[k], e[k + 1]));
-            t[k] += a;
-        }
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    for (int k = 0; k < 4; ++k) out[k] = t[k] / reps;
+    cg_profile_elim(S, reps, precond, out);
     slope_kernel_bytes(S, out + 4);
 }
 
-// The sensor grids' elimination inside real iterations of a live lsq_iterate state (no stop), events
-// between the launches as in cg_profile_slope: out8 = {ms of s = Bᵀ td, of z = R⁻ᵀ s, of y = R⁻¹ z, of
-// the apply pass, and their algorithmic bytes (sgrid_kernel_bytes)}, means over reps iterations.
+// The sensor grids' elimination inside real iterations: out8 = {ms of s = Bᵀ td, of z = R⁻ᵀ s, of
+// y = R⁻¹ z, of the apply pass, and their algorithmic bytes (sgrid_kernel_bytes)}, means over reps
+// iterations.
 void cg_profile_sgrid(System& S, int reps, int precond, double* out) {
-    if (!(S.cg_ready && S.cg_mode == precond))
-        throw std::invalid_argument("lsq_profile_sensor_grids: needs the live state of lsq_iterate with this precond");
+    cg_need_live(S, precond, "lsq_profile_sensor_grids");
     if (!sgrid_active(S)) throw std::invalid_argument("lsq_profile_sensor_grids: no sensor grids in the CGNR operator");
-    const CgGrids g = cg_grids(S, precond);
-    std::vector<hipEvent_t> ev(5 * reps);
-    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
-    for (int r = 0; r < reps; ++r) {
-        const int par = S.cg_parity;
-        const double* pold = cg_pold(S, par);
-        double* pnew = cg_pnew(S, par);
-        hipEvent_t* e = ev.data() + 5 * r;
-        cg_launch_normal(S, g, pold, pnew);
-        hipLaunchKernelGGL(k_cg_dmf_ad, dim3(g.gD), dim3(BLOCK), 0, S.stream, S.cst.p, S.dmf,
-                           reinterpret_cast<const double4*>(S.dmf_pt.p), pnew, S.cg_t.p, S.cg_part_t.p);
-        HIP_CHECK(hipEventRecord(e[0], S.stream));
-        sgrid_launch_btd(S, S.cst.p, S.cg_t.p);
-        HIP_CHECK(hipEventRecord(e[1], S.stream));
-        sgrid_launch_trsv_t(S, S.cst.p);
-        HIP_CHECK(hipEventRecord(e[2], S.stream));
-        sgrid_launch_trsv(S, S.cst.p);
-        HIP_CHECK(hipEventRecord(e[3], S.stream));
-        sgrid_launch_apply(S, S.cst.p, S.cg_t.p, 0, S.cg_part_t.p + g.gD);
-        HIP_CHECK(hipEventRecord(e[4], S.stream));
-        cg_launch_xr(S, g, pnew);
-        cg_launch_atdq(S);
-        cg_launch_alpha(S, g);
-        cg_launch_precond(S, g, precond);
-        hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(BLOCK), 0, S.stream, S.cst.p, S.cg_part_r.p, g.gB, 0, nullptr);
-        S.cg_parity = (S.cg_parity + 1) % CG_XK;
-    }
-    HIP_CHECK(hipStreamSynchronize(S.stream));
-    double t[4] = {0, 0, 0, 0};
-    for (int r = 0; r < reps; ++r) {
-        hipEvent_t* e = ev.data() + 5 * r;
-        for (int k = 0; k < 4; ++k) {
-            float a = 0.f;
-            HIP_CHECK(hipEventElapsedTime(&a, e[k], e[k + 1]));
-            t[k] += a;
-        }
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    for (int k = 0; k < 4; ++k) out[k] = t[k] / reps;
+    cg_profile_elim(S, reps, precond, out);
     sgrid_kernel_bytes(S, out + 4);
 }
 
@@ -2881,15 +2716,7 @@ void cg_apply_normal(System& S, const double* h_p, double* h_q) {
     S.cg_z.upload(h_p, nf, S.stream);
     S.cg_pb[0].zero(S.stream);
     cg_dmf_prepare(S);
-    if (S.cgh.colmode) {   // q = N_s p, t = Ad p, q += ATd t
-        cg_launch_normal(S, g, S.cg_pb[0].p, S.cg_pb[1].p);
-        cg_launch_data(S, g, S.cg_pb[0].p, S.cg_pb[1].p);
-        cg_launch_xr(S, g, S.cg_pb[1].p);
-        cg_launch_atdq(S);
-    } else {
-        cg_launch_data(S, g, S.cg_pb[0].p, S.cg_pb[1].p);
-        cg_launch_normal(S, g, S.cg_pb[0].p, S.cg_pb[1].p);
-    }
+    cg_launch_apply(S, g, S.cg_pb[0].p, S.cg_pb[1].p);
     KERNEL_CHECK();
     S.cg_q.download(h_q, nf, S.stream);
     HIP_CHECK(hipStreamSynchronize(S.stream));

@@ -653,8 +653,7 @@ void group_cg_init(Group& G, const double* const* h_b, const double* const* h_x0
                            cg_grids(*S, precond == 4 ? 3 : precond).gB, 6, nullptr, 0, 0, S->gsum.p);
     group_allreduce(G, 6, 1);
     for (System* S : G.ranks) {
-        const CgGrids g = cg_grids(*S, precond);
-        hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(BLOCK), 0, S->stream, S->cst.p, S->cg_part_r.p, g.gB, 1, S->gsum.p);
+        cg_launch_beta(*S, cg_grids(*S, precond), 1);
         S->cg_parity = 0;
     }
     group_halo_fwd_idx(G, sel_cgz, 0);
@@ -672,14 +671,7 @@ RedSpec red_rho_bj(System& S, int) { return {S.cg_part_r.p, cg_grids(S, 3).gB, 6
 RedSpec red_rho_jac(System& S, int) { return {S.cg_part_r.p, cg_grids(S, 1).gB, 6, nullptr, 0, 0}; }
 
 void group_cg_iteration(Group& G, int par, int precond) {
-    for (System* S : G.ranks) {
-        const CgGrids g = cg_grids(*S, precond);
-        const double* pold = cg_pold(*S, par);
-        double* pnew = cg_pnew(*S, par);
-        cg_launch_normal(*S, g, pold, pnew);
-        cg_launch_data(*S, g, pold, pnew);
-        cg_launch_atdq(*S);
-    }
+    for (System* S : G.ranks) cg_launch_apply(*S, cg_grids(*S, precond), cg_pold(*S, par), cg_pnew(*S, par));
     // partials reduced by the q pack, + all-reduce [pᵀN_s p, ‖t‖²] in the same RCCL group
     group_halo_rev_idx(G, sel_cgq, 0, 4, 2, red_gam);
     for (System* S : G.ranks) {
@@ -690,10 +682,7 @@ void group_cg_iteration(Group& G, int par, int precond) {
     if (precond == 4) group_mg_precond(G);
     // sᵀz partials reduced by the z pack; z to the ghosts + all-reduce sᵀz in one RCCL group
     group_halo_fwd_idx(G, sel_cgz, 0, 6, 1, precond == 1 ? red_rho_jac : red_rho_bj);
-    for (System* S : G.ranks) {
-        const CgGrids g = cg_grids(*S, precond);
-        hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(BLOCK), 0, S->stream, S->cst.p, S->cg_part_r.p, g.gB, 0, S->gsum.p);
-    }
+    for (System* S : G.ranks) cg_launch_beta(*S, cg_grids(*S, precond), 0);
 }
 
 // A process-per-GPU rank (one-rank group on RCCL, no device-group fence) replays each batch of

@@ -199,7 +199,7 @@ __global__ __launch_bounds__(BLOCK) void k_sg_diag(int64_t ntp, const int32_t* _
 // the grids take part in this system's CGNR operator
 inline bool sgrid_active(const System& S) { return S.sgrid.on && !S.dist && cg_use_dmf(S); }
 
-// the three launches of y = M⁻¹ Bᵀ src, one by one (the profile places events between them)
+// the three launches of y = M⁻¹ Bᵀ src
 void sgrid_launch_btd(const System& S, const CgState* st, const double* src) {
     const SgridData& G = S.sgrid;
     hipLaunchKernelGGL(k_sg_btd, dim3(grid_for(G.ntp, BLOCK / 64)), dim3(BLOCK), 0, S.stream, st, G.ntp, G.tr_ptr.p,
@@ -218,11 +218,15 @@ void sgrid_launch_trsv(const System& S, const CgState* st) {
                        G.node_grid.p, G.poff.p, G.moff.p, G.npad.p, G.Ri.p, G.z.p, G.y.p);
 }
 
-// y = M⁻¹ Bᵀ src (src per sorted point); s and z stay for the partials of k_sg_apply
-void sgrid_launch_reduce(const System& S, const CgState* st, const double* src) {
+// y = M⁻¹ Bᵀ src (src per sorted point); s and z stay for the partials of k_sg_apply.  marks
+// (nullable): the step's stages E0 (s = Bᵀ src), E1 (z = R⁻ᵀ s), E2 (y = R⁻¹ z)
+void sgrid_launch_reduce(const System& S, const CgState* st, const double* src, CgMarks* marks = nullptr) {
     sgrid_launch_btd(S, st, src);
+    cg_mark(marks, CG_E0, S.stream);
     sgrid_launch_trsv_t(S, st);
+    cg_mark(marks, CG_E1, S.stream);
     sgrid_launch_trsv(S, st);
+    cg_mark(marks, CG_E2, S.stream);
 }
 
 // mode 0: td −= W² B y; mode 1: td = −W² B y (after sgrid_launch_reduce); part (nullable): G.nbk
@@ -296,11 +300,11 @@ inline int64_t elim_npts(const System& S) { return S.sgrid.on ? S.sgrid.npts : S
 
 // the eliminated unknowns for the sums of src; part (nullable) as in elim_launch_step.  With sensor
 // grids the partials are written by the apply pass: elim_launch_apply must follow with the same part.
-void elim_launch_reduce(const System& S, const CgState* st, const double* src, double* part) {
+void elim_launch_reduce(const System& S, const CgState* st, const double* src, double* part, CgMarks* marks = nullptr) {
     if (S.sgrid.on)
-        sgrid_launch_reduce(S, st, src);
+        sgrid_launch_reduce(S, st, src, marks);
     else
-        bias_launch_reduce(S, st, src, part);
+        bias_launch_reduce(S, st, src, part, marks);
 }
 
 void elim_launch_apply(const System& S, const CgState* st, double* td, int mode, double* part) {
@@ -311,10 +315,12 @@ void elim_launch_apply(const System& S, const CgState* st, double* td, int mode,
 }
 
 // the elimination step on td (W² A_d p per sorted point): td ← W (I − Q) W A_d p; part: elim_nbk
-// partials of what the elimination takes off pᵀNp
-void elim_launch_step(const System& S, const CgState* st, double* td, double* part) {
-    elim_launch_reduce(S, st, td, part);
+// partials of what the elimination takes off pᵀNp; marks (nullable): the stages E0 … E2 of the reduce
+// and E3, the apply pass
+void elim_launch_step(const System& S, const CgState* st, double* td, double* part, CgMarks* marks = nullptr) {
+    elim_launch_reduce(S, st, td, part, marks);
     elim_launch_apply(S, st, td, 0, part);
+    cg_mark(marks, CG_E3, S.stream);
 }
 
 // the partials alone (the norm of W b in the general start): src is left as it is

@@ -248,6 +248,7 @@ class LSQSolver:
         d['bytes'] = {'cg_data': float(o[4]), 'cg_normal': float(o[5]), 'cg_update': float(o[6])}
         d['data_rows'] = 'matrix-free' if int(o[7]) & 1 else 'stored'
         d['normal_kernel'] = 'wave-strip' if int(o[7]) & 2 else 'ring'
+        d['normal_mode'] = 'column' if int(o[7]) & 4 else 'tile'
         return d
 
     def mg_info(self):

@@ -17,7 +17,7 @@ from lssurf_amd._native import NativeError
 from lssurf_amd.bias_functions import assign_bias_ID
 from lssurf_amd.constraint_functions import reference_epoch_keep_cols
 from lssurf_amd.smooth_fit import FitSystem
-from test_gpu_cgnr import _synthetic_system
+from test_gpu_cgnr import _profiler_runs_real_iterations, _synthetic_system, _times_are_positive
 
 pytestmark = pytest.mark.gpu
 REL, ABS = 1e-6, 1e-4
@@ -146,6 +146,27 @@ def test_clearing_the_biases_restores_every_bit(gpu_available):
     assert np.any(xb != res[1][0])
     assert np.array_equal(res[0][0], res[1][0]) and np.array_equal(res[0][1], res[1][1])
     assert res[0][2] == res[1][2]
+
+
+def test_profile_cg_with_biases_runs_real_iterations(gpu_available):
+    """profile_cg on the live state of iterate() with biases set: real steps (the same estimates after
+    16 as plain iterations give), positive times, the byte figures of the model iterate() reports."""
+    S, fs, w, rhs = _synthetic_system('t64')
+    keep = np.random.default_rng(18).random(fs.n_data) > 0.1
+    ids, c = _layouts(fs.n_data, keep, np.random.default_rng(19))['mixed']
+    try:
+        fs.solver.set_row_weight(w)
+        fs.solver.set_row_mask(np.concatenate([keep, np.ones(fs.n_con, bool)]))
+        fs.solver.set_data_bias(ids, c)
+        prof = _profiler_runs_real_iterations(fs.solver, rhs, fs.n_data, lambda reps: fs.solver.profile_cg(reps=reps),
+                                              lambda: fs.solver.set_data_bias(ids, c))
+        _times_are_positive([prof[k] for k in ('cg_data', 'cg_normal', 'cg_update', 'cg_scalars')])
+        with_bias = fs.solver.iterate(rhs, 1, precond=3, method=1, b_rows=fs.n_data)['bytes_per_iter']
+        assert sum(prof['bytes'].values()) == with_bias
+        fs.solver.set_data_bias(None, None)
+        assert with_bias > fs.solver.iterate(rhs, 1, precond=3, method=1, b_rows=fs.n_data)['bytes_per_iter']
+    finally:
+        fs.close()
 
 
 @functools.lru_cache(maxsize=None)

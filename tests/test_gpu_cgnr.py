@@ -222,6 +222,56 @@ def test_cgnr_2d_lin_op_system_exact_solution(gpu_available):
     assert np.max(np.abs(x - xs)) <= ABS
 
 
+EST = ('r1norm', 'arnorm', 'xnorm', 'anorm')
+
+
+def _profiler_runs_real_iterations(solver, rhs, b_rows, profile, restart, precond=3):
+    """A profiler that says it times real iterations must leave the run where plain iterations leave
+    it: 8 + 3 + 5 steps by iterate() against 8 steps, profile(3) and 5 steps, on one handle
+    (restart() clears the live state in between).  Three repetitions end off a whole x cycle.  The
+    step counts and the four estimates agree bit for bit.  Returns what profile(3) returned."""
+    def it(k):
+        return solver.iterate(rhs, k, precond=precond, method=1, b_rows=b_rows)
+
+    it(8)
+    it(3)
+    st_a = it(5)
+    restart()
+    it(8)
+    out = profile(3)
+    st_b = it(5)
+    print('plain', {f: st_a[f] for f in EST}, 'profiled', {f: st_b[f] for f in EST})
+    assert st_a['method'] == st_b['method'] == 1
+    assert st_a['iters'] == 16 and st_b['iters'] == 16
+    for f in EST:
+        assert st_a[f] == st_b[f], (f, st_a[f], st_b[f])
+    return out
+
+
+def _times_are_positive(ms):
+    assert all(np.isfinite(t) and t > 0 for t in ms), ms
+
+
+@pytest.mark.parametrize('precond', [1, 3])
+def test_profile_cg_runs_real_iterations(gpu_available, precond):
+    """profile_cg on the live state of iterate(): real steps (the same estimates after 16), four positive
+    times, and the byte figures of the model that iterate() reports."""
+    S, fs, w, rhs = _synthetic_system('t64')
+    keep = np.random.default_rng(41).random(fs.n_data) > 0.1
+    try:
+        fs.solver.set_row_weight(w)
+        fs.solver.set_row_mask(np.concatenate([keep, np.ones(fs.n_con, bool)]))
+        prof = _profiler_runs_real_iterations(
+            fs.solver, rhs, fs.n_data, lambda reps: fs.solver.profile_cg(reps=reps, precond=precond),
+            lambda: fs.solver.normal_apply(np.zeros(fs.n_full)), precond=precond)
+        _times_are_positive([prof[k] for k in ('cg_data', 'cg_normal', 'cg_update', 'cg_scalars')])
+        st = fs.solver.iterate(rhs, 1, precond=precond, method=1, b_rows=fs.n_data)
+        assert sum(prof['bytes'].values()) == st['bytes_per_iter']
+        assert prof['data_rows'] == 'matrix-free'
+    finally:
+        fs.close()
+
+
 @pytest.mark.parametrize('which', ['t64', 'tdense', 't15', 'nb_xt'])
 def test_matrix_free_data_rows_match_stored_rows(gpu_available, which, monkeypatch):
     """CGNR's matrix-free data rows (point subscripts sorted by cell, k_cg_dmf_*) against the

@@ -21,6 +21,7 @@ from lssurf_amd.smooth_fit import FitSystem
 from lssurf_amd.solver import LSQSolver
 from priors_common import prior_kwargs
 from test_gpu_bias import _host_reduced, _layouts
+from test_gpu_cgnr import _profiler_runs_real_iterations, _times_are_positive
 
 pytestmark = pytest.mark.gpu
 REL, ABS = 1e-6, 1e-4
@@ -242,6 +243,37 @@ def test_with_biases_the_two_terms_add(gpu_available):
         assert np.array_equal(q, fs.solver.normal_apply(pf)[keep_cols])
     finally:
         fs.close()
+
+
+def test_profile_extra_rows_runs_real_iterations(gpu_available):
+    """profile_extra_rows: refused without the live state of iterate() and without extra rows (the
+    handle goes on iterating); on the live state it runs real steps (the same estimates after 16 as
+    plain iterations give) and returns its four documented times, all positive."""
+    S, kw, keep_cols, w, rhs, keep, A = _base()
+    rng = np.random.default_rng(36)
+    csr = _csr(_random_rows(rng, 200))
+    wx = rng.uniform(0.5, 20., 200)
+    for extra in (True, False):
+        fs = _system(csr if extra else None)
+        b = np.r_[rhs, np.zeros(200)] if extra else rhs
+        try:
+            fs.solver.set_row_weight(np.r_[w, wx] if extra else w)
+            fs.solver.set_row_mask(np.concatenate([keep, np.ones(fs.n_con, bool)]))
+            with pytest.raises(NativeError, match='live state'):
+                fs.solver.profile_extra_rows(reps=3)
+            if extra:
+                prof = _profiler_runs_real_iterations(fs.solver, b, keep.size,
+                                                      lambda reps: fs.solver.profile_extra_rows(reps=reps),
+                                                      lambda: fs.solver.normal_apply(np.zeros(fs.n_full)))
+                assert list(prof) == ['k_xr_fwd', 'k_xr_atq', 'data_fwd', 'node_gather']
+                _times_are_positive(prof.values())
+            else:
+                st = fs.solver.iterate(b, 3, precond=3, method=1, b_rows=keep.size)
+                with pytest.raises(NativeError, match='no extra rows'):
+                    fs.solver.profile_extra_rows(reps=3)      # a live state, no extra rows
+                assert fs.solver.iterate(b, 2, precond=3, method=1, b_rows=keep.size)['iters'] == st['iters'] + 2
+        finally:
+            fs.close()
 
 
 def test_cleared_staging_restores_every_bit(gpu_available):

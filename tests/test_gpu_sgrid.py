@@ -17,7 +17,7 @@ from conftest import golden, golden_kwargs, golden_points
 from lssurf_amd._native import NativeError
 from lssurf_amd.constraint_functions import reference_epoch_keep_cols
 from lssurf_amd.smooth_fit import FitSystem
-from test_gpu_cgnr import _synthetic_system
+from test_gpu_cgnr import _profiler_runs_real_iterations, _synthetic_system, _times_are_positive
 
 pytestmark = pytest.mark.gpu
 REL, ABS = 1e-6, 1e-4
@@ -286,6 +286,40 @@ def test_clearing_the_grids_restores_every_bit(gpu_available):
             fs.close()
     assert np.any(xs != res[1][0])
     assert np.array_equal(res[0][0], res[1][0]) and res[0][1] == res[1][1]
+
+
+def test_profile_sensor_grids_runs_real_iterations(gpu_available):
+    """profile_sensor_grids: refused without the live state of iterate() and without grids (the handle
+    goes on iterating); on the live state it runs real steps (the same estimates after 16 as plain
+    iterations give), its four times are positive, and its four byte figures are the elimination's
+    share of bytes_per_iter."""
+    S, fs, w, rhs = _synthetic_system('t64')
+    keep = np.random.default_rng(36).random(fs.n_data) > 0.1
+    layout = _layouts(fs.n_data, keep, np.random.default_rng(37))['sizes']
+
+    def it(k):
+        return fs.solver.iterate(rhs, k, precond=3, method=1, b_rows=fs.n_data)
+
+    try:
+        fs.solver.set_row_weight(w)
+        fs.solver.set_row_mask(np.concatenate([keep, np.ones(fs.n_con, bool)]))
+        fs.solver.set_sensor_grids(*layout)
+        with pytest.raises(NativeError, match='live state'):
+            fs.solver.profile_sensor_grids(reps=3)
+        prof = _profiler_runs_real_iterations(fs.solver, rhs, fs.n_data,
+                                              lambda reps: fs.solver.profile_sensor_grids(reps=reps),
+                                              lambda: fs.solver.set_sensor_grids(*layout))
+        assert list(prof) == ['btd', 'trsv_t', 'trsv', 'apply']
+        _times_are_positive([ms for ms, _ in prof.values()])
+        with_grids = it(1)['bytes_per_iter']
+        fs.solver.set_sensor_grids(None, None, None, None, None)
+        without = it(1)
+        assert sum(b for _, b in prof.values()) == with_grids - without['bytes_per_iter']
+        with pytest.raises(NativeError, match='no sensor grids'):
+            fs.solver.profile_sensor_grids(reps=3)    # a live state, no grids
+        assert it(2)['iters'] == without['iters'] + 2
+    finally:
+        fs.close()
 
 
 @functools.lru_cache(maxsize=None)

@@ -21,7 +21,7 @@ from lssurf_amd.bias_functions import assign_bias_ID
 from lssurf_amd.constraint_functions import reference_epoch_keep_cols
 from lssurf_amd.data_slope_bias import slope_columns
 from lssurf_amd.smooth_fit import FitSystem
-from test_gpu_cgnr import _synthetic_system
+from test_gpu_cgnr import _profiler_runs_real_iterations, _synthetic_system, _times_are_positive
 
 pytestmark = pytest.mark.gpu
 REL, ABS = 1e-6, 1e-4
@@ -313,6 +313,41 @@ def test_clearing_the_slopes_restores_every_bit(gpu_available):
     assert np.any(xs != res[1][0])
     assert np.array_equal(res[0][0], res[1][0]) and np.array_equal(res[0][1], res[1][1])
     assert res[0][2] == res[1][2]
+
+
+def test_profile_data_slope_runs_real_iterations(gpu_available):
+    """profile_data_slope: refused without the live state of iterate() and without slopes (the handle
+    goes on iterating); on the live state it runs real steps (the same estimates after 16 as plain
+    iterations give), its four times are positive, and its four byte figures are the elimination's
+    share of bytes_per_iter."""
+    S, fs, w, rhs = _synthetic_system('t64')
+    keep = np.random.default_rng(26).random(fs.n_data) > 0.1
+    ids, c, grp, u, cs = _layouts(fs.n_data, keep, np.random.default_rng(27))['sizes']
+
+    def it(k):
+        return fs.solver.iterate(rhs, k, precond=3, method=1, b_rows=fs.n_data)
+
+    try:
+        fs.solver.set_row_weight(w)
+        fs.solver.set_row_mask(np.concatenate([keep, np.ones(fs.n_con, bool)]))
+        fs.solver.set_data_bias(ids, c)
+        fs.solver.set_data_slope(grp, u, cs)
+        with pytest.raises(NativeError, match='live state'):
+            fs.solver.profile_data_slope(reps=3)
+        prof = _profiler_runs_real_iterations(fs.solver, rhs, fs.n_data,
+                                              lambda reps: fs.solver.profile_data_slope(reps=reps),
+                                              lambda: fs.solver.set_data_slope(grp, u, cs))
+        assert list(prof) == ['chunk', 'rank', 'group', 'apply']
+        _times_are_positive([ms for ms, _ in prof.values()])
+        with_slopes = it(1)['bytes_per_iter']
+        fs.solver.set_data_bias(None, None)          # the biases and the slopes
+        without = it(1)
+        assert sum(b for _, b in prof.values()) == with_slopes - without['bytes_per_iter']
+        with pytest.raises(NativeError, match='no slopes'):
+            fs.solver.profile_data_slope(reps=3)      # a live state, no slopes
+        assert it(2)['iters'] == without['iters'] + 2
+    finally:
+        fs.close()
 
 
 @functools.lru_cache(maxsize=None)
