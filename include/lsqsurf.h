@@ -476,8 +476,7 @@ int lsq_profile_kernels(lsq_handle* h, int32_t reps, int32_t op, double* out8);
 int lsq_cg_available(lsq_handle* h, int32_t precond);
 int lsq_profile_cg(lsq_handle* h, int32_t reps, int32_t precond, double* out8);
 /* Multigrid (precond 4) test hooks.  lsq_mg_info: out[0] = levels L, then per level
- * (S0, S1, n_full, removed epoch) — cap must hold 1 + 4L values; with room for 2 + 4L, out[1 + 4L] =
- * the first level of the one-workgroup tail V-cycle (k_mg_tail), −1 for none.  lsq_mg_apply on level l's full
+ * (S0, S1, n_full, removed epoch) — cap must hold 1 + 4L values.  lsq_mg_apply on level l's full
  * column space (z0 grid then dz grid, in the system's order): what 0: y = N_l x (level 0: AᵀA;
  * coarse levels: Galerkin PᵀNP of the stencil rows + the (y, x)-lumped data rows), 1: y = the
  * V-cycle applied to x (level 0), 2: y[0] = the smoother's λ_max(M⁻¹N) estimate of level l.

@@ -1839,7 +1839,6 @@ CgP cg_pbufs(const System& S) {
 double* cg_pnew(System& S, int ph) { return S.cg_pb[ph].p; }
 const double* cg_pold(const System& S, int ph) { return S.cg_pb[(ph + CG_XK - 1) % CG_XK].p; }
 double mg_bytes(const System& S, double op0_bytes);
-void mg_check(System& S);
 struct MgDistInfo;
 bool mg_build(System& S, std::string& why, const MgDistInfo* di = nullptr);
 void mg_setup(System& S);
@@ -2452,7 +2451,6 @@ int cg_solve(System& S, const double* h_b, double* h_x, const lsq_opts& o, lsq_s
     HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    if (precond == 4) mg_check(S);
     if (stats) {
         cg_fill_stats(h, stats);
         stats->time_s = ms * 1e-3;
@@ -2496,7 +2494,6 @@ int cg_iterate(System& S, const double* h_b, int64_t iters, const lsq_opts& o, l
     HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    if (precond == 4) mg_check(S);
     if (stats) {
         cg_fill_stats(h, stats);
         stats->time_s = ms * 1e-3;

@@ -95,22 +95,6 @@ struct MgLevel {
     DBuf<double> hb;
 };
 
-struct MgCoarseDev {   // a small coarse level as k_mg_coarse sees it (device copy, MgHier::pdev)
-    MgGeom geo;
-    MgTab tz, td;
-    BlkAffine aff;
-    const int32_t *oz, *od, *dz, *dd;   // k_mg_direct's offsets and column deltas
-    const double *coef, *B, *dN;
-    const lf_t* Lf;
-    double *x, *r, *q, *d, *res;
-    int64_t npad;
-    int32_t coarsest, lpc;
-};
-struct MgBar {            // grid barrier of k_mg_coarse (count, generation, timeout flag)
-    unsigned int count, gen;
-    int err, pad;
-};
-
 struct MgHier {
     ~MgHier() {
         if (rg) (void)hipGraphExecDestroy(rg);
@@ -126,13 +110,11 @@ struct MgHier {
     int deg0 = 2, deg = 1;       // Chebyshev degree on level 0 / on coarse levels (MG_DEG0, MG_DEG; env overrides)
     int deg0_pre = 2;            // level 0's pre-smoothing degree (LSQ_MG_DEG0_PRE, development: ≠ deg0
                                  // makes the V-cycle non-symmetric)
-    int fuse = 5;                // bit 0: the first smoothing step in the CG update; bit 1: coarse
-                                 // residuals inside the restriction; bit 2: the restriction inside
-                                 // the next level's first smoothing step (k_mg_restrict_smooth, round
-                                 // 6: C4 solve 0.1158 → 0.1143 s, c4y8 0.0421 → 0.0417 s, bitwise
-                                 // equal; `profiles/r06_mg_rsfuse_ab.txt`); bit 3: the direct levels'
-                                 // operator kernel writes the residual (no MG_RES pass; measured
-                                 // within the spread, off: `profiles/r06_mg_resop_ab.txt`) (LSQ_MG_FUSE)
+    int fuse = 5;                // bit 0: the first smoothing step in the CG update; bit 2: the
+                                 // restriction inside the next level's first smoothing step
+                                 // (k_mg_restrict_smooth, round 6: C4 solve 0.1158 → 0.1143 s, c4y8
+                                 // 0.0421 → 0.0417 s, bitwise equal; `profiles/r06_mg_rsfuse_ab.txt`)
+                                 // (LSQ_MG_FUSE, masked with 5)
     DBuf<double> lam;            // λ estimate per level
     DBuf<double> scal;           // op-kernel β (power steps: scale − 1; V-cycle: 0)
     DBuf<CgState> mst;           // stop = 0: the set-up ops run regardless of the solve's state
@@ -157,14 +139,6 @@ struct MgHier {
     bool mixed = false;
     MgMix mix{};
     DBuf<double> xdinv, xpart;   // 1 / diag(N) of the z0 columns; operator partial scratch
-    // the small coarse levels [pl, L) in one persistent launch (k_mg_coarse; pl = −1: none)
-    int pl = -1, pnwg = 0;
-    DBuf<struct MgCoarseDev> pdev;
-    // the levels [tl, L) in one workgroup with LDS-resident vectors (k_mg_tail; tl = −1: none)
-    int tl = -1;
-    size_t tlds = 0;
-    DBuf<struct MgCoarseDev> tdev;
-    DBuf<struct MgBar> pbar;
     MgTab xtz{}, xtd{};          // S.mx level 0's class tables (tile layout) for its exact node blocks
     DBuf<double> xcoef, xB, xRi;
     DBuf<int64_t> xptr;
@@ -194,9 +168,6 @@ constexpr int MG_COARSE = 5;     // coarsest level: at most this many nodes per 
 // columns is one GEMV.  Square lattices (C4: 9² × 13 = 1 053 columns) keep the ≤ 5-per-side rule.
 constexpr int64_t MG_COARSE_COLS = 1024;
 constexpr int64_t MG_DIRECT = 1 << 18;   // levels with at most this many columns: k_mg_direct (LSQ_MG_DIRECT)
-// levels with at most this many columns: one k_mg_coarse launch (LSQ_MG_PERSIST; 0: off — the
-// default: measured slower, see k_mg_coarse)
-constexpr int64_t MG_PERSIST = 0;
 constexpr int64_t MG_TILE_MIN = 1 << 16; // levels with more columns: k_mg_tile + k_mg_edge (LSQ_MG_TILE)
 constexpr int MG_NB_MAX = 48;    // lumped data doubles per node (3·nt, nt ≤ 16)
 constexpr int MG_XZERO = 1, MG_RES = 2, MG_POWER = 4, MG_RHO = 8;   // k_mg_smooth modes
@@ -220,55 +191,20 @@ __device__ __forceinline__ int64_t mg_col(const MgGeom& G, int64_t node, int t) 
     return t < 0 ? G.colz + node : G.cold + node * G.nt + t;
 }
 
-// res_f = r − q − (B x)_f at fine column (node, t) of a coarse level: B the node's lumped data
-// block (arrow + tridiagonal, k_mg_block_build's layout), in the order k_mg_smooth's MG_RES pass
-// sums it
-// (qc: the column's q value — k_mg_direct passes the one it has just summed)
-__device__ __forceinline__ double mg_res_fine_q(const MgGeom& F, int64_t node, int t, const double* __restrict__ r,
-                                                double qc, const double* __restrict__ x,
-                                                const double* __restrict__ B, int nbB) {
-    const double* Bn = B + node * nbB;
-    const int nt = F.nt;
-    const int64_t c = mg_col(F, node, t);
-    double bx;
-    if (t < 0) {
-        bx = Bn[0] * x[c];
-        for (int t2 = 0; t2 < nt; ++t2)
-            if (t2 != F.tref) bx += Bn[1 + t2] * x[mg_col(F, node, t2)];
-    } else {
-        bx = (F.has_z ? Bn[1 + t] * x[mg_col(F, node, -1)] : 0.0) + Bn[1 + nt + t] * x[c];
-        if (t + 1 < nt && t + 1 != F.tref) bx += Bn[1 + 2 * nt + t] * x[mg_col(F, node, t + 1)];
-        if (t - 1 >= 0 && t - 1 != F.tref) bx += Bn[1 + 2 * nt + t - 1] * x[mg_col(F, node, t - 1)];
-    }
-    return (r[c] - qc) - bx;
-}
-__device__ __forceinline__ double mg_res_fine(const MgGeom& F, int64_t node, int t, const double* __restrict__ r,
-                                              const double* __restrict__ q, const double* __restrict__ x,
-                                              const double* __restrict__ B, int nbB) {
-    return mg_res_fine_q(F, node, t, r, q[mg_col(F, node, t)], x, B, nbB);
-}
-// k_mg_direct's residual output (MgHier::fuse bit 3): res = r − N_s x − B x written instead of q
-struct MgResOut {
-    const double *r, *x, *B;
-    double* res;
-    int nbB;
-};
-
 // r_c = P_ℓᵀ res_f: each coarse column gathers the ≤ 3×3 fine nodes of its prolongation support.
-// qf non-null, B null (level 0, whose operator has no lumped block): res_f = rf − qf; B non-null
-// (coarse levels): res_f = rf − qf − (B x)_f — the residual pass of the smoother fused in.
+// qf non-null (level 0, whose operator has no lumped block): res_f = rf − qf; qf null (coarse
+// levels): rf is the residual of the smoother's MG_RES pass.
 // MG_RU columns per thread and loop trip, their gathers issued together (one column per trip left
 // the level-0 restriction and prolongation latency-bound at ~2.8 TB/s)
 #ifndef MG_RU_DEF
 #define MG_RU_DEF 4
 #endif
 constexpr int MG_RU = MG_RU_DEF;   // -DMG_RU_DEF=…: A/B builds
-// (bodies of the level kernels take the workgroup's index among nblk: k_mg_coarse runs them all in
-// one persistent launch)
-__device__ __forceinline__ void mg_restrict_body(const MgGeom& F, const MgGeom& C, const double* __restrict__ rf,
-                                                 const double* __restrict__ qf, const double* __restrict__ xf,
-                                                 const double* __restrict__ Bf, int nbB, double* __restrict__ rc,
-                                                 int bid, int nblk) {
+__global__ __launch_bounds__(BLOCK) void k_mg_restrict(const CgState* __restrict__ st, MgGeom F, MgGeom C,
+                                                       const double* __restrict__ rf, const double* __restrict__ qf,
+                                                       double* __restrict__ rc) {
+    if (st->stop) return;
+    const int bid = blockIdx.x, nblk = gridDim.x;
     const int64_t stride = (int64_t)nblk * BLOCK;
     for (int64_t c0 = (int64_t)bid * BLOCK + threadIdx.x; c0 < C.n_full; c0 += MG_RU * stride) {
         double acc[MG_RU];
@@ -288,10 +224,8 @@ __device__ __forceinline__ void mg_restrict_body(const MgGeom& F, const MgGeom& 
                 for (int dx = -1; dx <= 1; ++dx) {
                     const int fx = 2 * x + dx;
                     if (fx < 0 || fx >= F.S1) continue;
-                    const int64_t fnode = (int64_t)fy * F.S1 + fx;
-                    const int64_t fc = mg_col(F, fnode, t);
-                    const double res = Bf ? mg_res_fine(F, fnode, t, rf, qf, xf, Bf, nbB) : (qf ? rf[fc] - qf[fc] : rf[fc]);
-                    acc[u] += ((dy ? 0.5 : 1.0) * (dx ? 0.5 : 1.0)) * res;
+                    const int64_t fc = mg_col(F, (int64_t)fy * F.S1 + fx, t);
+                    acc[u] += ((dy ? 0.5 : 1.0) * (dx ? 0.5 : 1.0)) * (qf ? rf[fc] - qf[fc] : rf[fc]);
                 }
             }
         }
@@ -300,17 +234,12 @@ __device__ __forceinline__ void mg_restrict_body(const MgGeom& F, const MgGeom& 
             if (c0 + u * stride < C.n_full) rc[c0 + u * stride] = acc[u];
     }
 }
-__global__ __launch_bounds__(BLOCK) void k_mg_restrict(const CgState* __restrict__ st, MgGeom F, MgGeom C,
-                                                       const double* __restrict__ rf, const double* __restrict__ qf,
-                                                       const double* __restrict__ xf, const double* __restrict__ Bf,
-                                                       int nbB, double* __restrict__ rc) {
-    if (st->stop) return;
-    mg_restrict_body(F, C, rf, qf, xf, Bf, nbB, rc, blockIdx.x, gridDim.x);
-}
 
 // x_f += P_ℓ x_c: each fine column gathers its ≤ 2×2 coarse parents
-__device__ __forceinline__ void mg_prolong_body(const MgGeom& F, const MgGeom& C, const double* __restrict__ xc,
-                                                double* __restrict__ xf, int bid, int nblk) {
+__global__ __launch_bounds__(BLOCK) void k_mg_prolong(const CgState* __restrict__ st, MgGeom F, MgGeom C,
+                                                      const double* __restrict__ xc, double* __restrict__ xf) {
+    if (st->stop) return;
+    const int bid = blockIdx.x, nblk = gridDim.x;
     const int64_t stride = (int64_t)nblk * BLOCK;
     for (int64_t c0 = (int64_t)bid * BLOCK + threadIdx.x; c0 < F.n_full; c0 += MG_RU * stride) {
         double acc[MG_RU], xo[MG_RU];
@@ -337,11 +266,6 @@ __device__ __forceinline__ void mg_prolong_body(const MgGeom& F, const MgGeom& C
         for (int u = 0; u < MG_RU; ++u)
             if (on[u]) xf[c0 + u * stride] = xo[u] + acc[u];
     }
-}
-__global__ __launch_bounds__(BLOCK) void k_mg_prolong(const CgState* __restrict__ st, MgGeom F, MgGeom C,
-                                                      const double* __restrict__ xc, double* __restrict__ xf) {
-    if (st->stop) return;
-    mg_prolong_body(F, C, xc, xf, blockIdx.x, gridDim.x);
 }
 
 // Ranks (mg_build_dist): level 0 is the window F (global node rows wa + local), level 1 the global
@@ -801,7 +725,7 @@ __device__ __forceinline__ double mg_restrict_col(const MgGeom& F, const MgGeom&
     double acc = 0.0;
     if (t >= 0 && t == C.tref) return acc;
     const int y = (int)fdiv((uint32_t)node, C.fd_s1), x = (int)(node - (int64_t)y * C.S1);
-    for (int dy = -1; dy <= 1; ++dy) {   // the order and weights of mg_restrict_body
+    for (int dy = -1; dy <= 1; ++dy) {   // the order and weights of k_mg_restrict
         const int fy = 2 * y + dy;
         if (fy < 0 || fy >= F.S0) continue;
         for (int dx = -1; dx <= 1; ++dx) {
@@ -826,11 +750,12 @@ __device__ __forceinline__ void mg_smooth_body(int64_t nb, int npks, const BlkAf
                                                double* __restrict__ x, double* __restrict__ d,
                                                double* __restrict__ res, const double* __restrict__ lam, int mode,
                                                int step, double* __restrict__ part, double* __restrict__ part2,
-                                               const uint8_t* __restrict__ live, int bid, int nblk,
-                                               MgSmoothLds<HB>& sm, const MgRestrictSrc* rs = nullptr) {
+                                               const uint8_t* __restrict__ live, MgSmoothLds<HB>& sm,
+                                               const MgRestrictSrc* rs = nullptr) {
     auto& LR = sm.LR;
     auto& LB = sm.LB;
     auto& SX = sm.SX;
+    const int bid = blockIdx.x, nblk = gridDim.x;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int L = kslot, W = 64 / L;
     const int grp = lane / L, j = lane - grp * L, gbase = grp * L;
@@ -962,7 +887,7 @@ __global__ __launch_bounds__(BLOCK) void k_mg_smooth(const CgState* __restrict__
     if (st->stop) return;
     __shared__ MgSmoothLds<HB> sm;
     mg_smooth_body<K, HB, CM>(nb, npks, aff, kslot, sl, nbB, Lf, B, r, q, x, d, res, lam, mode, step, part, part2, live,
-                              blockIdx.x, gridDim.x, sm);
+                              sm);
 }
 // the restriction into level ℓ+1 and that level's first pre-smoothing step (from x = 0, the
 // direction not stored: degree ≤ 2) in one launch; r of level ℓ+1 is written for the later passes
@@ -975,7 +900,7 @@ __global__ __launch_bounds__(BLOCK) void k_mg_restrict_smooth(const CgState* __r
     __shared__ MgSmoothLds<false> sm;
     mg_smooth_body<K, false, MG_XZERO | MG_NOD, true>(nb, npks, aff, kslot, sl, 0, Lf, nullptr, nullptr, nullptr, x,
                                                       nullptr, nullptr, lam, MG_XZERO | MG_NOD, 0, nullptr, nullptr,
-                                                      nullptr, blockIdx.x, gridDim.x, sm, &rs);
+                                                      nullptr, sm, &rs);
 }
 
 // Small coarse levels (n_full ≤ MG_DIRECT): q = N_s p gathered per column straight from the class
@@ -984,13 +909,17 @@ __global__ __launch_bounds__(BLOCK) void k_mg_restrict_smooth(const CgState* __r
 // with few columns still spreads over the chip and each lane's gather chain stays short — one
 // lane per column left a 125-long dependent load chain (~30 µs whatever the level size).
 template <int LPC>
-__device__ __forceinline__ void mg_direct_body(const MgGeom& G, const MgTab& tz, const MgTab& td,
-                                               const int32_t* __restrict__ offz, const int32_t* __restrict__ offd,
-                                               const int32_t* __restrict__ djz, const int32_t* __restrict__ djd,
-                                               const double* __restrict__ coef, const double* __restrict__ z,
-                                               const double* __restrict__ pold, double beta,
-                                               double* __restrict__ pnew, double* __restrict__ q, int bid, int nblk,
-                                               int ra = 0, int rb = 1 << 30, const MgResOut* ro = nullptr) {
+__global__ __launch_bounds__(BLOCK) void k_mg_direct(const CgState* __restrict__ st, MgGeom G, MgTab tz, MgTab td,
+                                                     const int32_t* __restrict__ offz,
+                                                     const int32_t* __restrict__ offd,
+                                                     const int32_t* __restrict__ djz, const int32_t* __restrict__ djd,
+                                                     const double* __restrict__ coef, const double* __restrict__ z,
+                                                     const double* __restrict__ pold,
+                                                     const double* __restrict__ betap, double* __restrict__ pnew,
+                                                     double* __restrict__ q, int ra, int rb) {
+    if (st->stop) return;
+    const double beta = betap ? *betap : st->beta;
+    const int bid = blockIdx.x, nblk = gridDim.x;
     const int sub = threadIdx.x % LPC;
     const int64_t per = (int64_t)nblk * (BLOCK / LPC);
     // every lane of a column group runs the same trip count (shuffles need the whole group)
@@ -1026,27 +955,10 @@ __device__ __forceinline__ void mg_direct_body(const MgGeom& G, const MgTab& tz,
 #pragma unroll
         for (int m = LPC / 2; m >= 1; m /= 2) acc += __shfl_xor(acc, m, LPC);
         if (live && sub == 0) {
-            if (ro) {   // the smoother's MG_RES pass, in its order (mg_res_fine); q is not stored
-                if (!(t >= 0 && t == G.tref)) ro->res[c] = mg_res_fine_q(G, node, t, ro->r, acc, ro->x, ro->B, ro->nbB);
-            } else {
-                q[c] = acc;
-            }
+            q[c] = acc;
             if (pnew) pnew[c] = pold ? z[c] + beta * pold[c] : z[c];
         }
     }
-}
-template <int LPC>
-__global__ __launch_bounds__(BLOCK) void k_mg_direct(const CgState* __restrict__ st, MgGeom G, MgTab tz, MgTab td,
-                                                     const int32_t* __restrict__ offz,
-                                                     const int32_t* __restrict__ offd,
-                                                     const int32_t* __restrict__ djz, const int32_t* __restrict__ djd,
-                                                     const double* __restrict__ coef, const double* __restrict__ z,
-                                                     const double* __restrict__ pold,
-                                                     const double* __restrict__ betap, double* __restrict__ pnew,
-                                                     double* __restrict__ q, int ra, int rb, MgResOut ro) {
-    if (st->stop) return;
-    mg_direct_body<LPC>(G, tz, td, offz, offd, djz, djd, coef, z, pold, betap ? *betap : st->beta, pnew, q, blockIdx.x,
-                        gridDim.x, ra, rb, ro.res ? &ro : nullptr);
 }
 
 // Coarse levels (ℓ ≥ 1): q = N_s p in two kernels on two streams, each writing its own nodes.
@@ -1171,13 +1083,17 @@ __device__ __forceinline__ void mg_edge_node(uint32_t k, int S0, int S1, int K0,
     x = j < K1 ? j : S1 - 2 * K1 + j;
 }
 
-// the boundary-class items of a level, workgroup bid of nblk (grid-stride over the items)
+// the boundary-class items of a level (grid-stride over the items)
 template <int LPC>
-__device__ __forceinline__ void mg_edge_body(const MgGeom& G, const MgTab& tz, const MgTab& td,
-                                             const int32_t* __restrict__ offz, const int32_t* __restrict__ offd,
-                                             const double* __restrict__ coef, const double* __restrict__ z,
-                                             const double* __restrict__ pold, double beta, double* __restrict__ q,
-                                             int bid, int nblk, int ra = 0, int rb = 1 << 30) {
+__global__ __launch_bounds__(BLOCK) void k_mg_edge(const CgState* __restrict__ st, MgGeom G, MgTab tz, MgTab td,
+                                                   const int32_t* __restrict__ offz, const int32_t* __restrict__ offd,
+                                                   const double* __restrict__ coef, const double* __restrict__ z,
+                                                   const double* __restrict__ pold,
+                                                   const double* __restrict__ betap, double* __restrict__ q, int ra,
+                                                   int rb) {
+    if (st->stop) return;
+    const double beta = betap ? *betap : st->beta;
+    const int bid = blockIdx.x, nblk = gridDim.x;
     const int sub = threadIdx.x % LPC;
     const int64_t nz = tz.on ? mg_edge_count(G.S0, G.S1, tz.K0, tz.K1) : 0;
     const int64_t nd = td.on ? mg_edge_count(G.S0, G.S1, td.K0, td.K1) * td.S2 : 0;
@@ -1216,17 +1132,6 @@ __device__ __forceinline__ void mg_edge_body(const MgGeom& G, const MgTab& tz, c
         for (int m = LPC / 2; m >= 1; m /= 2) acc += __shfl_xor(acc, m, LPC);
         if (live && sub == 0) q[c] = acc;
     }
-}
-
-template <int LPC>
-__global__ __launch_bounds__(BLOCK) void k_mg_edge(const CgState* __restrict__ st, MgGeom G, MgTab tz, MgTab td,
-                                                   const int32_t* __restrict__ offz, const int32_t* __restrict__ offd,
-                                                   const double* __restrict__ coef, const double* __restrict__ z,
-                                                   const double* __restrict__ pold,
-                                                   const double* __restrict__ betap, double* __restrict__ q, int ra,
-                                                   int rb) {
-    if (st->stop) return;
-    mg_edge_body<LPC>(G, tz, td, offz, offd, coef, z, pold, betap ? *betap : st->beta, q, blockIdx.x, gridDim.x, ra, rb);
 }
 
 // the interior tiles (k_mg_edge: the boundary-class items, on the side stream — run after the
@@ -1417,8 +1322,11 @@ __global__ __launch_bounds__(BLOCK) void k_mg_gram(const double* __restrict__ Ri
 }
 
 // y = M x, one wave per row (coalesced row reads)
-__device__ __forceinline__ void mg_gemv_body(const double* __restrict__ M, int64_t n, int64_t ld,
-                                             const double* __restrict__ x, double* __restrict__ y, int bid, int nblk) {
+__global__ __launch_bounds__(BLOCK) void k_mg_gemv(const CgState* __restrict__ st, const double* __restrict__ M,
+                                                   int64_t n, int64_t ld, const double* __restrict__ x,
+                                                   double* __restrict__ y) {
+    if (st->stop) return;
+    const int bid = blockIdx.x, nblk = gridDim.x;
     const int lane = threadIdx.x & 63;
     for (int64_t i = (int64_t)bid * 4 + (threadIdx.x >> 6); i < n; i += (int64_t)nblk * 4) {
         double s = 0.0;
@@ -1426,12 +1334,6 @@ __device__ __forceinline__ void mg_gemv_body(const double* __restrict__ M, int64
         s = wave_sum(s);
         if (lane == 0) y[i] = s;
     }
-}
-__global__ __launch_bounds__(BLOCK) void k_mg_gemv(const CgState* __restrict__ st, const double* __restrict__ M,
-                                                   int64_t n, int64_t ld, const double* __restrict__ x,
-                                                   double* __restrict__ y) {
-    if (st->stop) return;
-    mg_gemv_body(M, n, ld, x, y, blockIdx.x, gridDim.x);
 }
 
 // power step scalars: λ = max(λ, x·Nx) (x is M-normalised from the second step on), next scale
@@ -1959,63 +1861,6 @@ struct MgDistInfo {
 
 bool mg_build_mixed(System& S, std::string& why);
 
-// k_mg_coarse for the levels [pl, L) when every one of them is a direct-kernel level (or the
-// coarsest) and level pl has at most LSQ_MG_PERSIST (MG_PERSIST) columns: their device views, the
-// barrier, one workgroup per CU; each level's lanes per column so that one pass covers its columns
-void mg_persist_setup(System& S, MgHier& H) {
-    static const int64_t pmax = getenv("LSQ_MG_PERSIST") ? atoll(getenv("LSQ_MG_PERSIST")) : MG_PERSIST;
-    const int L = (int)H.lev.size();
-    H.pl = -1;
-    if (pmax <= 0 || L < 3) return;
-    int pl = L - 1;
-    while (pl - 1 >= 1 && (H.lev[pl - 1].direct || H.lev[pl - 1].coarsest) && !H.lev[pl - 1].tile &&
-           H.lev[pl - 1].geo.n_full <= pmax)
-        --pl;
-    if (pl > L - 2) return;
-    int dev = 0, cus = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    static const int pwg = getenv("LSQ_MG_PWG") ? atoi(getenv("LSQ_MG_PWG")) : 0;   // workgroups (0: one per CU)
-    // LSQ_MG_PWG = 1: the small levels in ONE workgroup (its grid barriers reduce to workgroup
-    // barriers plus one uncontended atomic; VERDICT r3 item 4a); default one workgroup per CU
-    H.pnwg = std::max(1, std::min(pwg > 0 ? pwg : cus, std::min(cus, 256)));
-    const int64_t lanes = (int64_t)H.pnwg * BLOCK;
-    std::vector<MgCoarseDev> v;
-    for (int l = pl; l < L; ++l) {
-        MgLevel& V = H.lev[l];
-        MgCoarseDev d{};
-        d.geo = V.geo;
-        d.tz = V.tz;
-        d.td = V.td;
-        d.aff = V.aff;
-        const int nz = H.gz >= 0 ? V.tz.noff : 0, nd = H.gd >= 0 ? V.td.noff : 0;
-        d.oz = V.offs.p;
-        d.od = d.oz + 3 * nz;
-        d.dz = d.od + 3 * nd;
-        d.dd = d.dz + nz;
-        d.coef = V.coef.p;
-        d.B = V.B.p;
-        d.dN = V.dN.p;
-        d.Lf = V.Lf.p;
-        d.x = V.x.p;
-        d.r = V.r.p;
-        d.q = V.q.p;
-        d.d = V.d.p;
-        d.res = V.res.p;
-        d.npad = V.npad;
-        d.coarsest = V.coarsest ? 1 : 0;
-        d.lpc = V.geo.n_full * 64 <= lanes ? 64 : V.geo.n_full * 16 <= lanes ? 16 : 4;
-        v.push_back(d);
-    }
-    H.pdev.alloc((int64_t)v.size());
-    H.pdev.upload(v.data(), (int64_t)v.size(), S.stream);
-    H.pbar.alloc(1);
-    H.pbar.zero(S.stream);
-    H.pl = pl;
-}
-
-void mg_tail_setup(System& S, MgHier& H);
-
 // k_mg_tile_kt's compressed interior-class rows (MgLevel::tkc) from a tiled level's column-mode
 // table, when they hold it exactly: every 3-D grid has 12 epochs with the 5-class dim-2 layout
 // (K2 = 2), every t of a class has the class row's taps, and every tap that reaches outside the
@@ -2157,7 +2002,7 @@ bool mg_build(System& S, std::string& why, const MgDistInfo* di) {
     if (const char* e = getenv("LSQ_MG_DEG")) H->deg = std::max(1, atoi(e));
     if (const char* e = getenv("LSQ_MG_DEG0")) H->deg0 = std::max(1, atoi(e));
     H->deg0_pre = getenv("LSQ_MG_DEG0_PRE") ? std::max(1, atoi(getenv("LSQ_MG_DEG0_PRE"))) : H->deg0;
-    if (const char* e = getenv("LSQ_MG_FUSE")) H->fuse = atoi(e);
+    if (const char* e = getenv("LSQ_MG_FUSE")) H->fuse = atoi(e) & 5;
     H->nt = nt;
     g0.tref = H->tref;
     H->nbB = std::max(2, (3 * nt + 1) & ~1);
@@ -2368,8 +2213,6 @@ bool mg_build(System& S, std::string& why, const MgDistInfo* di) {
     H->res0.zero(S.stream);
     H->err.alloc(1);
     H->ndead.alloc(1);
-    if (!di && !H->var) mg_persist_setup(S, *H);
-    if (!H->var && H->pl < 0) mg_tail_setup(S, *H);
     HIP_CHECK(hipStreamSynchronize(S.stream));
     S.mg = guard.release();
     if (!di) mg_var_coarse(S);
@@ -2510,354 +2353,6 @@ bool mg_build_mixed(System& S, std::string& why) {
     return true;
 }
 
-// ---- the small coarse levels in one launch ---------------------------------------------------------
-// The small levels' kernels are a few µs of launch and drain each (~20 of them per V-cycle on the
-// levels ≤ 33² at C4, ~104 µs).  k_mg_coarse runs the V-cycle from level l0 down to the coarsest
-// and back with the same bodies (mg_smooth_body, mg_direct_body, mg_restrict_body, mg_gemv_body,
-// mg_prolong_body) separated by grid barriers, all workgroups resident (a barrier that times out
-// sets MgBar::err, which the host reads after the solve).  Measured at C4 (levels ≤ 33², 15
-// phases): 517 µs with a workgroup per CU, the C4 solve 0.138 → 0.158 s (256 workgroups), 0.161 /
-// 0.151 / 0.147 s (16 / 32 / 64), 0.143 s (levels ≤ 17² only), 0.1385 s (≤ 9²) — a same-address
-// barrier costs more than the graph's kernel boundary it replaces, so it is off (MG_PERSIST = 0).
-
-__device__ __forceinline__ bool mg_grid_sync(MgBar* g, unsigned int nwg, unsigned int& gen) {
-    __shared__ int ok;
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        ok = 1;
-        const unsigned int arrived = atomicAdd(&g->count, 1u) + 1u;
-        if (arrived == nwg) {
-            atomicExch(&g->count, 0u);
-            __threadfence();
-            atomicAdd(&g->gen, 1u);
-        } else {
-            long spins = 0;
-            while (__hip_atomic_load(&g->gen, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == gen) {
-                if (++spins > (1L << 22) || __hip_atomic_load(&g->err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                    atomicExch(&g->err, 1);
-                    ok = 0;
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(1);
-            }
-        }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        ++gen;
-    }
-    __syncthreads();
-    return ok != 0;
-}
-
-template <int K, int CM>
-__device__ __forceinline__ void mg_coarse_smooth(const MgCoarseDev& V, int npks, int kslot, const MgSlots& sl, int nbB,
-                                                 const double* lam, int mode, int step, int bid, int nblk,
-                                                 MgSmoothLds<true>& sm) {
-    mg_smooth_body<K, true, CM>(V.geo.nodes, npks, V.aff, kslot, sl, nbB, V.Lf, V.B, V.r, V.q, V.x, V.d, V.res, lam,
-                                mode, step, nullptr, nullptr, nullptr, bid, nblk, sm);
-}
-
-__device__ __forceinline__ void mg_coarse_op(const MgCoarseDev& V, int bid, int nblk) {
-    if (V.lpc == 64)
-        mg_direct_body<64>(V.geo, V.tz, V.td, V.oz, V.od, V.dz, V.dd, V.coef, V.x, nullptr, 0.0, nullptr, V.q, bid, nblk);
-    else if (V.lpc == 16)
-        mg_direct_body<16>(V.geo, V.tz, V.td, V.oz, V.od, V.dz, V.dd, V.coef, V.x, nullptr, 0.0, nullptr, V.q, bid, nblk);
-    else
-        mg_direct_body<4>(V.geo, V.tz, V.td, V.oz, V.od, V.dz, V.dd, V.coef, V.x, nullptr, 0.0, nullptr, V.q, bid, nblk);
-}
-
-// levels [l0, L) (lv[0] = level l0), Chebyshev degree deg, in the order of mg_vcycle
-template <int K>
-__global__ __launch_bounds__(BLOCK) void k_mg_coarse(const CgState* __restrict__ st, const MgCoarseDev* __restrict__ lv,
-                                                     int l0, int L, int deg, int fuse2, int kslot, MgSlots sl, int nbB,
-                                                     int npks, const double* __restrict__ lam, MgBar* bar) {
-    if (st->stop) return;
-    __shared__ MgSmoothLds<true> sm;
-    __shared__ unsigned int gen0;
-    if (threadIdx.x == 0) gen0 = __hip_atomic_load(&bar->gen, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    unsigned int gen = gen0;
-    const int bid = blockIdx.x, nb = gridDim.x;
-#define MG_SYNC() \
-    if (!mg_grid_sync(bar, nb, gen)) return;
-    for (int l = l0; l + 1 < L; ++l) {
-        const MgCoarseDev& V = lv[l - l0];
-        const MgCoarseDev& C = lv[l + 1 - l0];
-        if (deg <= 2)
-            mg_coarse_smooth<K, MG_XZERO | MG_NOD>(V, npks, kslot, sl, nbB, lam + l, MG_XZERO | MG_NOD, 0, bid, nb, sm);
-        else
-            mg_coarse_smooth<K, -1>(V, npks, kslot, sl, nbB, lam + l, MG_XZERO, 0, bid, nb, sm);
-        MG_SYNC();
-        for (int k = 1; k < deg; ++k) {
-            mg_coarse_op(V, bid, nb);
-            MG_SYNC();
-            mg_coarse_smooth<K, -1>(V, npks, kslot, sl, nbB, lam + l,
-                                    (k == 1 ? MG_DX : 0) | (k == deg - 1 ? MG_NOD : 0) | (k > 1 ? MG_NEEDD : 0), k, bid,
-                                    nb, sm);
-            MG_SYNC();
-        }
-        mg_coarse_op(V, bid, nb);
-        MG_SYNC();
-        if (!fuse2) {
-            mg_coarse_smooth<K, MG_RES>(V, npks, kslot, sl, nbB, lam + l, MG_RES, 0, bid, nb, sm);
-            MG_SYNC();
-            mg_restrict_body(V.geo, C.geo, V.res, nullptr, nullptr, nullptr, nbB, C.r, bid, nb);
-        } else {
-            mg_restrict_body(V.geo, C.geo, V.r, V.q, V.x, V.B, nbB, C.r, bid, nb);
-        }
-        MG_SYNC();
-    }
-    {
-        const MgCoarseDev& V = lv[L - 1 - l0];
-        mg_gemv_body(V.dN, V.geo.n_full, V.npad, V.r, V.x, bid, nb);
-        MG_SYNC();
-    }
-    for (int l = L - 2; l >= l0; --l) {
-        const MgCoarseDev& V = lv[l - l0];
-        const MgCoarseDev& C = lv[l + 1 - l0];
-        mg_prolong_body(V.geo, C.geo, C.x, V.x, bid, nb);
-        MG_SYNC();
-        for (int k = 0; k < deg; ++k) {
-            mg_coarse_op(V, bid, nb);
-            MG_SYNC();
-            if (k == 0 && deg == 1)
-                mg_coarse_smooth<K, MG_NOD>(V, npks, kslot, sl, nbB, lam + l, MG_NOD, 0, bid, nb, sm);
-            else
-                mg_coarse_smooth<K, -1>(V, npks, kslot, sl, nbB, lam + l,
-                                        (k == deg - 1 ? MG_NOD : 0) | (k > 0 ? MG_NEEDD : 0), k, bid, nb, sm);
-            if (l > l0 || k + 1 < deg) MG_SYNC();
-        }
-    }
-#undef MG_SYNC
-}
-
-// ---- the small coarse levels in ONE workgroup, vectors in LDS (k_mg_tail, round 6) -------------
-// Below ~4 k columns a level's kernels are launch- and latency-bound: every one of the ~7 launches
-// of a level costs 4–6 µs whatever its size, so the three or four smallest levels and the coarsest
-// solve cost 120–200 µs per V-cycle (C4; one rank's window at N = 8, with its launch gaps).  Here one
-// workgroup of MG_TT threads runs the V-cycle of the levels [tl, L) with every level's x (and r below
-// tl) in LDS, phases separated by workgroup barriers: the stencil operator by column from the class
-// table (k_mg_direct's row), the node-block smoothing by node (k_mg_smooth's products, one thread
-// per node), the restriction with the residual r − q − B x formed in place, the prolongation and
-// the coarsest level's dense inverse.  In exact arithmetic the same V-cycle as the per-level
-// launches; the sums are grouped differently (ulp-level).  The persistent multi-workgroup variant
-// (k_mg_coarse) paid a grid barrier per phase and kept the vectors in global memory.
-// Measured and dropped (round 6, `profiles/r06_mg_tail_ab.txt`): C4 multigrid solve 0.156 s with
-// the tail (LSQ_MG_TAIL=4096: levels 17², 9², 5²) against 0.120 s without, c4y8 0.074 against
-// 0.047 s — the same 47 / 50 iterations.  One CU cannot stream the levels' class-table rows: a
-// column's 125 coefficient loads come from L2 at ~1 µs latency with 8 waves to hide it, so the 17²
-// operator alone takes ~0.25 ms where the per-level launch spreads it over the chip in 11 µs.
-constexpr int MG_TT = 512;                 // threads of k_mg_tail (2 waves per SIMD: 256 VGPRs)
-// levels with at most this many columns (LSQ_MG_TAIL; default 0: off — measured slower, below)
-constexpr int64_t MG_TAIL = 0;
-
-template <int K>
-__device__ __forceinline__ void mgt_smooth(const MgCoarseDev& V, const double* __restrict__ r, double* __restrict__ x,
-                                           const double* __restrict__ q, int kslot, const MgSlots& sl, int nbB,
-                                           int npks, double c2, bool xzero) {
-    const int nt = sl.nt;
-    for (int64_t b = threadIdx.x; b < V.geo.nodes; b += MG_TT) {
-        int64_t col[K];
-        double xv[K], rv[K];
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            col[j] = j < kslot ? V.aff.base[j] + b * V.aff.stride[j] : 0;
-            xv[j] = (j < kslot && !xzero) ? x[col[j]] : 0.0;
-            rv[j] = j < kslot ? r[col[j]] : 0.0;
-        }
-        double res[K];
-        const double* Bn = V.B + b * nbB;
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            if (j >= kslot) {
-                res[j] = 0.0;
-                continue;
-            }
-            if (xzero) {
-                res[j] = rv[j];
-                continue;
-            }
-            const int tj = sl.t[j];
-            auto pick = [&](int s) {   // x of slot s (a runtime slot: unrolled selects, no scratch)
-                double v = 0.0;
-#pragma unroll
-                for (int i = 0; i < K; ++i) v = i == s ? xv[i] : v;
-                return v;
-            };
-            double bx;
-            if (tj < 0) {
-                bx = Bn[0] * xv[j];
-#pragma unroll
-                for (int i = 0; i < K; ++i)
-                    if (i < kslot && sl.t[i] >= 0) bx += Bn[1 + sl.t[i]] * xv[i];
-            } else {
-                bx = (sl.zs >= 0 ? Bn[1 + tj] * pick(sl.zs) : 0.0) + Bn[1 + nt + tj] * xv[j];
-                if (sl.hi[j] >= 0) bx += Bn[1 + 2 * nt + tj] * pick(sl.hi[j]);
-                if (sl.lo[j] >= 0) bx += Bn[1 + 2 * nt + tj - 1] * pick(sl.lo[j]);
-            }
-            res[j] = (rv[j] - q[col[j]]) - bx;
-        }
-        const lf_t* M = V.Lf + b * npks;
-        double w[K];   // w = R_b⁻ᵀ res: w_j = Σ_{i≤j} (R_b⁻¹)_ij res_i
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            double a = 0.0;
-#pragma unroll
-            for (int i = 0; i <= j; ++i) a += (j < kslot ? (double)lf_val(M[j * (j + 1) / 2 + i]) : 0.0) * res[i];
-            w[j] = a;
-        }
-#pragma unroll
-        for (int j = 0; j < K; ++j) {   // z = R_b⁻¹ w: z_j = Σ_{i≥j} (R_b⁻¹)_ji w_i
-            double z = 0.0;
-#pragma unroll
-            for (int i = j; i < K; ++i) z += (i < kslot ? (double)lf_val(M[i * (i + 1) / 2 + j]) : 0.0) * w[i];
-            if (j < kslot) x[col[j]] = xv[j] + c2 * z;
-        }
-    }
-}
-
-// q = N_s x over every column of a tail level (x in LDS)
-__device__ __forceinline__ void mgt_op(const MgCoarseDev& V, const double* __restrict__ x, double* __restrict__ q) {
-    const MgGeom& G = V.geo;
-    for (int64_t c = threadIdx.x; c < G.n_full; c += MG_TT) {
-        int64_t node;
-        int t;
-        mg_decode(G, c, node, t);
-        const int y = (int)fdiv((uint32_t)node, G.fd_s1), xx = (int)(node - (int64_t)y * G.S1), tt = t < 0 ? 0 : t;
-        const MgTab& T = t < 0 ? V.tz : V.td;
-        const int32_t* off = t < 0 ? V.oz : V.od;
-        const int32_t* dj = t < 0 ? V.dz : V.dd;
-        double acc = 0.0;
-        if (T.on) {
-            const double* cr = mg_row(T, V.coef, y, xx, tt);
-            const bool inner = y >= T.hy && y < G.S0 - T.hy && xx >= T.hx && xx < G.S1 - T.hx && tt >= T.ht &&
-                               tt < T.S2 - T.ht;
-#pragma unroll 8
-            for (int o = 0; o < T.noff; ++o) {   // 8 taps' coefficient loads in flight per lane
-                int64_t j = c + dj[o];
-                double cf = cr[o];
-                if (!inner) {
-                    const int yy = y + off[3 * o], x2 = xx + off[3 * o + 1], t2 = tt + off[3 * o + 2];
-                    const bool ok = yy >= 0 && yy < G.S0 && x2 >= 0 && x2 < G.S1 && t2 >= 0 && t2 < T.S2;
-                    j = ok ? j : c;
-                    cf = ok ? cf : 0.0;
-                }
-                acc += cf * x[j];
-            }
-        }
-        q[c] = acc;
-    }
-}
-
-template <int K>
-__global__ __launch_bounds__(MG_TT) void k_mg_tail(const CgState* __restrict__ st, const MgCoarseDev* __restrict__ lv,
-                                                   int nl, int kslot, MgSlots sl, int nbB, int npks,
-                                                   const double* __restrict__ lam) {
-    if (st->stop) return;
-    extern __shared__ double mgt_lds[];
-    // LDS: x of every level, then r of levels ≥ 1, then q (the first level's size); the offsets in
-    // LDS too (a runtime-indexed pointer array would live in scratch)
-    __shared__ int64_t xoff[8], roff[8], qoff;
-    if (threadIdx.x == 0) {
-        int64_t o = 0;
-        for (int l = 0; l < nl; ++l) {
-            xoff[l] = o;
-            o += lv[l].geo.n_full;
-        }
-        for (int l = 1; l < nl; ++l) {
-            roff[l] = o;
-            o += lv[l].geo.n_full;
-        }
-        qoff = o;
-    }
-    __syncthreads();
-    auto X = [&](int l) { return mgt_lds + xoff[l]; };
-    auto R = [&](int l) { return mgt_lds + roff[l]; };
-    double* Q = mgt_lds + qoff;
-    const int64_t o = qoff;
-    const double* r0 = lv[0].r;
-    auto rl = [&](int l) -> const double* { return l ? R(l) : r0; };
-    auto c2_of = [&](int l) {
-        const double lmax = 1.1 * lam[l], lmin = 0.1 * lmax;
-        return 1.0 / (0.5 * (lmax + lmin));
-    };
-    for (int64_t c = threadIdx.x; c < o; c += MG_TT) mgt_lds[c] = 0.0;   // removed columns stay 0
-    __syncthreads();
-    for (int l = 0; l + 1 < nl; ++l) {   // down: pre-smoothing from x = 0, residual, restriction
-        const MgCoarseDev& V = lv[l];
-        const MgGeom &F = V.geo, &C = lv[l + 1].geo;
-        mgt_smooth<K>(V, rl(l), X(l), Q, kslot, sl, nbB, npks, c2_of(l), true);
-        __syncthreads();
-        mgt_op(V, X(l), Q);
-        __syncthreads();
-        for (int64_t c = threadIdx.x; c < F.n_full; c += MG_TT) {   // Q ← r − q − B x (in place)
-            int64_t node;
-            int t;
-            mg_decode(F, c, node, t);
-            if (t >= 0 && t == F.tref) continue;
-            Q[c] = mg_res_fine(F, node, t, rl(l), Q, X(l), V.B, nbB);
-        }
-        __syncthreads();
-        for (int64_t c = threadIdx.x; c < C.n_full; c += MG_TT) {   // r_{l+1} = Pᵀ res
-            int64_t node;
-            int t;
-            mg_decode(C, c, node, t);
-            double acc = 0.0;
-            if (!(t >= 0 && t == C.tref)) {
-                const int y = (int)fdiv((uint32_t)node, C.fd_s1), x = (int)(node - (int64_t)y * C.S1);
-                for (int dy = -1; dy <= 1; ++dy) {
-                    const int fy = 2 * y + dy;
-                    if (fy < 0 || fy >= F.S0) continue;
-                    for (int dx = -1; dx <= 1; ++dx) {
-                        const int fx = 2 * x + dx;
-                        if (fx < 0 || fx >= F.S1) continue;
-                        acc += ((dy ? 0.5 : 1.0) * (dx ? 0.5 : 1.0)) * Q[mg_col(F, (int64_t)fy * F.S1 + fx, t)];
-                    }
-                }
-            }
-            R(l + 1)[c] = acc;
-        }
-        __syncthreads();
-    }
-    {   // coarsest: x = N⁻¹ r with the explicit inverse, a wave per row
-        const MgCoarseDev& V = lv[nl - 1];
-        const int64_t n = V.geo.n_full;
-        const int lane = threadIdx.x & 63;
-        const double* rr = rl(nl - 1);
-        for (int64_t i = threadIdx.x >> 6; i < n; i += MG_TT / 64) {
-            double sum = 0.0;
-            for (int64_t j = lane; j < n; j += 64) sum += V.dN[i * V.npad + j] * rr[j];
-            sum = wave_sum(sum);
-            if (lane == 0) X(nl - 1)[i] = sum;
-        }
-        __syncthreads();
-    }
-    for (int l = nl - 2; l >= 0; --l) {   // up: prolongation, post-smoothing
-        const MgCoarseDev& V = lv[l];
-        const MgGeom &F = V.geo, &C = lv[l + 1].geo;
-        for (int64_t c = threadIdx.x; c < F.n_full; c += MG_TT) {
-            int64_t node;
-            int t;
-            mg_decode(F, c, node, t);
-            if (t >= 0 && t == F.tref) continue;
-            const int y = (int)fdiv((uint32_t)node, F.fd_s1), x = (int)(node - (int64_t)y * F.S1);
-            const int ya = y >> 1, xa = x >> 1, ny = (y & 1) ? 2 : 1, nx = (x & 1) ? 2 : 1;
-            const double wy = (y & 1) ? 0.5 : 1.0, wx = (x & 1) ? 0.5 : 1.0;
-            double acc = 0.0;
-            for (int a = 0; a < ny; ++a)
-                for (int b = 0; b < nx; ++b) acc += (wy * wx) * X(l + 1)[mg_col(C, (int64_t)(ya + a) * C.S1 + xa + b, t)];
-            X(l)[c] += acc;
-        }
-        __syncthreads();
-        mgt_op(V, X(l), Q);
-        __syncthreads();
-        mgt_smooth<K>(V, rl(l), X(l), Q, kslot, sl, nbB, npks, c2_of(l), false);
-        __syncthreads();
-    }
-    double* xo = lv[0].x;   // the first level's x for the prolongation launched after this kernel
-    for (int64_t c = threadIdx.x; c < lv[0].geo.n_full; c += MG_TT) xo[c] = X(0)[c];
-}
-
 // ---- host: launches ------------------------------------------------------------------------------
 
 // coarse levels: q += the Galerkin rows of the field-valued z0 parts (after the level's stencil
@@ -2883,10 +2378,8 @@ void mg_launch_xr(System& S, MgHier& H, const CgState* st, const double* p, doub
 // (β from betap; p_old may be null; p written to pnew when non-null).  The operand the x-edge
 // correction and the data rows read is pnew, or z.
 // ra, rb: node rows computed (a rank's partitioned coarse level: its owned rows; tile / direct only)
-// ro (direct levels only): write the residual r − N_s z − B z instead of q (k_mg_direct)
 void mg_launch_op(System& S, MgHier& H, int l, const CgState* st, const double* z, const double* pold,
-                  const double* betap, double* pnew, double* q, int ra = 0, int rb = 1 << 30,
-                  const MgResOut& ro = MgResOut{}) {
+                  const double* betap, double* pnew, double* q, int ra = 0, int rb = 1 << 30) {
     MgLevel& V = H.lev[l];
     if (V.tile) {   // boundary-class nodes beside the interior tiles (disjoint writes of q)
         // LSQ_MG_TILE_DBG (development phase switches; results wrong when set): 1 skip the
@@ -2924,17 +2417,13 @@ void mg_launch_op(System& S, MgHier& H, int l, const CgState* st, const double* 
         const dim3 grid((unsigned)std::min<int64_t>((nf + cpb - 1) / cpb, 8 * MAX_GRID));
         if (lpc == 64)
             hipLaunchKernelGGL(k_mg_direct<64>, grid, dim3(BLOCK), 0, S.stream, st, V.geo, V.tz, V.td, oz, od, dz, dd,
-                               V.coef.p, z, pold, betap, pnew, q, ra, rb, ro);
+                               V.coef.p, z, pold, betap, pnew, q, ra, rb);
         else if (lpc == 16)
             hipLaunchKernelGGL(k_mg_direct<16>, grid, dim3(BLOCK), 0, S.stream, st, V.geo, V.tz, V.td, oz, od, dz, dd,
-                               V.coef.p, z, pold, betap, pnew, q, ra, rb, ro);
+                               V.coef.p, z, pold, betap, pnew, q, ra, rb);
         else
             hipLaunchKernelGGL(k_mg_direct<4>, grid, dim3(BLOCK), 0, S.stream, st, V.geo, V.tz, V.td, oz, od, dz, dd,
-                               V.coef.p, z, pold, betap, pnew, q, ra, rb, ro);
-        if (ro.res) {   // the caller's residual: no field-valued parts on this level (checked there)
-            if (H.var) throw std::logic_error("mg_launch_op: residual output with field-valued parts");
-            return;
-        }
+                               V.coef.p, z, pold, betap, pnew, q, ra, rb);
         mg_launch_var(S, H, l, st, z, pold, betap, q);
         return;
     }
@@ -3028,91 +2517,9 @@ void mg_launch_smooth(System& S, MgHier& H, int l, const CgState* st, const MgVe
                        v.x, v.d, v.res, lam, mode, step, part, part2, live);
 }
 
-// k_mg_tail for the levels [tl, L): every one a direct-kernel level (or the coarsest), at most
-// LSQ_MG_TAIL (MG_TAIL) columns, at most 8 levels, and their vectors within the device's LDS per
-// workgroup (hipFuncAttributeMaxDynamicSharedMemorySize above 64 KB)
-void mg_tail_setup(System& S, MgHier& H) {
-    static const int64_t tmax = getenv("LSQ_MG_TAIL") ? atoll(getenv("LSQ_MG_TAIL")) : MG_TAIL;
-    const int L = (int)H.lev.size();
-    H.tl = -1;
-    if (tmax <= 0 || L < 3 || H.kslot > BJ_LANES) return;
-    int tl = L - 1;
-    while (tl - 1 >= 1 && (H.lev[tl - 1].direct || H.lev[tl - 1].coarsest) && !H.lev[tl - 1].tile &&
-           H.lev[tl - 1].geo.n_full <= tmax && L - (tl - 1) <= 8)
-        --tl;
-    if (tl > L - 2 || !H.lev[L - 1].coarsest) return;
-    int64_t words = H.lev[tl].geo.n_full;   // q scratch
-    for (int l = tl; l < L; ++l) words += H.lev[l].geo.n_full * (l > tl ? 2 : 1);
-    const size_t bytes = (size_t)words * sizeof(double);
-    int dev = 0, lim = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    if (hipDeviceGetAttribute(&lim, hipDeviceAttributeSharedMemPerBlockOptin, dev) != hipSuccess || lim <= 0) {
-        (void)hipGetLastError();
-        HIP_CHECK(hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-    }
-    if ((int64_t)bytes > (int64_t)lim) return;
-    const void* kf = H.kslot <= 12 ? reinterpret_cast<const void*>(k_mg_tail<12>) : reinterpret_cast<const void*>(k_mg_tail<BJ_LANES>);
-    if (bytes > 65536 && hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return;
-    }
-    std::vector<MgCoarseDev> v;
-    for (int l = tl; l < L; ++l) {
-        MgLevel& V = H.lev[l];
-        MgCoarseDev d{};
-        d.geo = V.geo;
-        d.tz = V.tz;
-        d.td = V.td;
-        d.aff = V.aff;
-        const int nz = H.gz >= 0 ? V.tz.noff : 0, nd = H.gd >= 0 ? V.td.noff : 0;
-        d.oz = V.offs.p;
-        d.od = d.oz + 3 * nz;
-        d.dz = d.od + 3 * nd;
-        d.dd = d.dz + nz;
-        d.coef = V.coef.p;
-        d.B = V.B.p;
-        d.dN = V.dN.p;
-        d.Lf = V.Lf.p;
-        d.x = V.x.p;
-        d.r = V.r.p;
-        d.q = V.q.p;
-        d.d = V.d.p;
-        d.res = V.res.p;
-        d.npad = V.npad;
-        d.coarsest = V.coarsest ? 1 : 0;
-        v.push_back(d);
-    }
-    H.tdev.alloc((int64_t)v.size());
-    H.tdev.upload(v.data(), (int64_t)v.size(), S.stream);
-    H.tlds = bytes;
-    H.tl = tl;
-}
-
 // one V-cycle from level l: x_l = V(r_l).  Level 0 reads r = S.cg_s and writes x = S.cg_z; its
 // last smoothing step also leaves the partials of rᵀx in S.cg_part_r (ρ of the CG step).
 void mg_vcycle(System& S, MgHier& H, int l, const CgState* st, bool x1_ready = false) {
-    if (l > 0 && l == H.tl && l > H.lp) {   // the smallest levels: one workgroup, LDS-resident vectors
-        const int npk = H.kslot * (H.kslot + 1) / 2, npks = lf_stride(npk), nl = (int)H.lev.size() - l;
-        if (H.kslot <= 12)
-            hipLaunchKernelGGL(k_mg_tail<12>, dim3(1), dim3(MG_TT), H.tlds, S.stream, st, H.tdev.p, nl, H.kslot, H.sl,
-                               H.nbB, npks, H.lam.p + l);
-        else
-            hipLaunchKernelGGL(k_mg_tail<BJ_LANES>, dim3(1), dim3(MG_TT), H.tlds, S.stream, st, H.tdev.p, nl, H.kslot,
-                               H.sl, H.nbB, npks, H.lam.p + l);
-        return;
-    }
-    if (l > 0 && l == H.pl) {   // the small coarse levels: one persistent launch
-        const int npk = H.kslot * (H.kslot + 1) / 2, npks = lf_stride(npk);
-        if (H.kslot <= 12)
-            hipLaunchKernelGGL(k_mg_coarse<12>, dim3(H.pnwg), dim3(BLOCK), 0, S.stream, st, H.pdev.p, l,
-                               (int)H.lev.size(), H.deg, (H.fuse & 2) ? 1 : 0, H.kslot, H.sl, H.nbB, npks, H.lam.p,
-                               H.pbar.p);
-        else
-            hipLaunchKernelGGL(k_mg_coarse<BJ_LANES>, dim3(H.pnwg), dim3(BLOCK), 0, S.stream, st, H.pdev.p, l,
-                               (int)H.lev.size(), H.deg, (H.fuse & 2) ? 1 : 0, H.kslot, H.sl, H.nbB, npks, H.lam.p,
-                               H.pbar.p);
-        return;
-    }
     MgLevel& V = H.lev[l];
     const MgVec v = mg_vecs(S, H, l);
     const double* zero = H.scal.p + 1;   // β = 0
@@ -3130,31 +2537,22 @@ void mg_vcycle(System& S, MgHier& H, int l, const CgState* st, bool x1_ready = f
         mg_launch_op(S, H, l, st, v.x, nullptr, zero, nullptr, v.q);
         mg_launch_smooth(S, H, l, st, v, (k == 1 ? MG_DX : 0) | (k == dpre - 1 ? MG_NOD : 0), k, nullptr, nullptr);
     }
-    MgLevel& C = H.lev[l + 1];   // restriction of res = r − q (− B x on coarse levels), formed on the fly
-    // fuse bit 2: the restriction inside level ℓ+1's first smoothing step (a smoothing level below:
-    // not the coarsest, the one-workgroup tail or the persistent levels; residual without B)
+    MgLevel& C = H.lev[l + 1];
+    // restriction of the residual: level 0's r − q formed on the fly, a coarse level's res = r − q − B x
+    // by an MG_RES pass of the smoother.  fuse bit 2: the restriction inside level ℓ+1's first
+    // smoothing step (a smoothing level below, not the coarsest)
     const int lc = l + 1;
-    const bool rsf = (H.fuse & 4) && H.kslot <= 12 && H.deg <= 2 && !C.coarsest && !(lc == H.tl && lc > H.lp) &&
-                     lc != H.pl && !(l && (H.fuse & 2));
-    // fuse bit 3: on a direct level the operator kernel writes the residual itself (no MG_RES pass)
-    const bool resop = rsf && l && (H.fuse & 8) && V.direct && !V.tile && !H.var;
-    if (resop)
-        mg_launch_op(S, H, l, st, v.x, nullptr, zero, nullptr, v.q, 0, 1 << 30, MgResOut{v.r, v.x, V.B.p, v.res, H.nbB});
-    else
-        mg_launch_op(S, H, l, st, v.x, nullptr, zero, nullptr, v.q);
+    const bool rsf = (H.fuse & 4) && H.kslot <= 12 && H.deg <= 2 && !C.coarsest;
+    mg_launch_op(S, H, l, st, v.x, nullptr, zero, nullptr, v.q);
+    if (l) mg_launch_smooth(S, H, l, st, v, MG_RES, 0, nullptr, nullptr);
     if (rsf) {
-        if (l && !resop) mg_launch_smooth(S, H, l, st, v, MG_RES, 0, nullptr, nullptr);   // res = r − q − B x
         const int npk = H.kslot * (H.kslot + 1) / 2, npks = lf_stride(npk);
         const MgRestrictSrc rs{V.geo, C.geo, l ? v.res : v.r, l ? nullptr : v.q, C.r.p};
         hipLaunchKernelGGL(k_mg_restrict_smooth<12>, dim3(C.gB), dim3(BLOCK), 0, S.stream, st, C.geo.nodes, npks, C.aff,
                            H.kslot, H.sl, (const lf_t*)C.Lf.p, C.x.p, H.lam.p + lc, rs);
-    } else if (l && !(H.fuse & 2)) {
-        mg_launch_smooth(S, H, l, st, v, MG_RES, 0, nullptr, nullptr);   // res = r − q − B x
-        hipLaunchKernelGGL(k_mg_restrict, dim3(grid_for(C.geo.n_full)), dim3(BLOCK), 0, S.stream, st, V.geo, C.geo,
-                           v.res, nullptr, nullptr, nullptr, H.nbB, C.r.p);
     } else {
-        hipLaunchKernelGGL(k_mg_restrict, dim3(grid_for(C.geo.n_full)), dim3(BLOCK), 0, S.stream, st, V.geo, C.geo, v.r,
-                           v.q, l ? v.x : nullptr, l ? V.B.p : nullptr, H.nbB, C.r.p);
+        hipLaunchKernelGGL(k_mg_restrict, dim3(grid_for(C.geo.n_full)), dim3(BLOCK), 0, S.stream, st, V.geo, C.geo,
+                           l ? v.res : v.r, l ? nullptr : v.q, C.r.p);
     }
     mg_vcycle(S, H, lc, st, rsf);
     hipLaunchKernelGGL(k_mg_prolong, dim3(grid_for(V.geo.n_full)), dim3(BLOCK), 0, S.stream, st, V.geo, C.geo, C.x.p,
@@ -3222,18 +2620,6 @@ void mg_vcycle_graph(System& S, MgHier& H, int l) {
         H.rg_l = l;
     }
     HIP_CHECK(hipGraphLaunch(H.rg, S.stream));
-}
-
-// after a solve: a grid barrier of k_mg_coarse that timed out (its workgroups were not all
-// resident) leaves the V-cycle's coarse correction undefined — fail loudly
-void mg_check(System& S) {
-    if (!S.mg || S.mg->pl < 0) return;
-    MgBar b{};
-    HIP_CHECK(hipMemcpy(&b, S.mg->pbar.p, sizeof(b), hipMemcpyDeviceToHost));
-    if (b.err) {
-        S.mg->pbar.zero(S.stream);
-        throw std::runtime_error("multigrid: the coarse-level grid barrier timed out (LSQ_MG_PERSIST=0 avoids it)");
-    }
 }
 
 // Per-solve set-up for the current row weights / mask (after cg_dmf_prepare refreshed the points'
@@ -3550,7 +2936,6 @@ int mg_info(System& S, int64_t* out, int64_t cap) {
             out[3 + 4 * l] = HX.lev[l - 1].geo.n_full;
             out[4 + 4 * l] = HX.tref;
         }
-        if (cap >= 2 + 4 * L) out[1 + 4 * L] = HX.tl >= 0 ? HX.tl + 1 : -1;
         return 0;
     }
     const int64_t L = (int64_t)H.lev.size();
@@ -3562,7 +2947,6 @@ int mg_info(System& S, int64_t* out, int64_t cap) {
         out[3 + 4 * l] = H.lev[l].geo.n_full;
         out[4 + 4 * l] = H.tref;
     }
-    if (cap >= 2 + 4 * L) out[1 + 4 * L] = H.tl;
     return 0;
 }
 

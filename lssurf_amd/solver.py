@@ -256,13 +256,7 @@ class LSQSolver:
         o = np.zeros(1 + 4 * 32, np.int64)
         self._check(self._L.lsq_mg_info(self._h, ptr(o), o.size), 'lsq_mg_info')
         L = int(o[0])
-        self._mg_tail = int(o[1 + 4 * L])
         return [tuple(int(v) for v in o[1 + 4 * l:4 + 4 * l]) for l in range(L)], int(o[4])
-
-    def mg_tail_level(self):
-        """First level of the multigrid's one-workgroup tail V-cycle (k_mg_tail), −1 for none."""
-        self.mg_info()
-        return self._mg_tail
 
     def mg_apply(self, level, what, x=None):
         """Multigrid test hook: what 0 → N_l x on level l's full column space; 1 → V-cycle(x)
