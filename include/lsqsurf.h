@@ -298,6 +298,31 @@ int lsq_set_band_order(lsq_handle* h, int64_t n, const int32_t* perm);
 int lsq_cov_band(lsq_handle* h, const int32_t* perm, double* E, int64_t n_ops, const int64_t* op_ptr,
                  const int32_t* op_col, const double* op_val, double* op_err, int64_t* info);
 
+/* lsq_cov_band for a banded system with a dense BORDER (smooth_fit's data and slope biases: a
+ * bias column couples every node its track crosses, so no order makes the whole AᵀA banded).
+ * perm has one entry per compact column: its first n - n_border positions are the band columns in
+ * a banded order, its last n_border positions the border columns.  With
+ *   AᵀA = [ N  Bᵗ ]    N = R̃ᵀR̃ (the band factor of the principal submatrix, as lsq_cov_band_window)
+ *         [ B  C  ]    Y = R̃⁻ᵀBᵗ,  S = C − YᵀY = R_SᵀR_S (n_border × n_border dense),  V = R̃⁻¹(Y R_S⁻¹)
+ *   var(band column j)   = (N⁻¹)_jj + ‖V_j·‖²   (the first term: lsq_cov_band's sweeps)
+ *   var(border column j) = ‖(R_S⁻¹)_j·‖²
+ *   var(op row q)        = q N⁻¹ qᵀ + ‖q V‖²     (op rows must hold band columns only)
+ * on the equilibrated matrix; Y and V (n_pad × k_pad, k_pad = n_border rounded up to 64) are
+ * stored, one workgroup per panel of 64 right-hand sides runs each substitution on f64 MFMA, and
+ * every sum has a fixed order (results are bitwise equal run to run).  E per compact column and
+ * op_err as lsq_cov_band.  n_border = 0 is lsq_cov_band itself.  At most LSQ_BORDER_MAX border
+ * columns: beyond, and when Y and V (2·n_pad·k_pad·8 bytes, plus 2·k_pad²·8) do not fit 0.8 of the
+ * device's free memory beside the band, the call is refused (-5) before the border is allocated.
+ * -2: perm is not a permutation, an op row reaches a border column, n_border < 0 or > n, or the
+ * border block S is not positive definite (a border column without a kept data row or a weighted
+ * constraint row).  info (nullable, 10): [0..5] as lsq_cov_band ([5]: the band's sweeps only),
+ * k_pad, device bytes of the border buffers, µs of the border steps (host wall clock), f64 flops
+ * of the two substitutions. */
+#define LSQ_BORDER_MAX 4096
+int lsq_cov_band_bordered(lsq_handle* h, const int32_t* perm, int64_t n_border, double* E, int64_t n_ops,
+                          const int64_t* op_ptr, const int32_t* op_col, const double* op_val, double* op_err,
+                          int64_t* info);
+
 /* The same for a WINDOW of the columns (compute_E at scale, lssurf_amd/errors.py method 'window'):
  * perm[0..n_win) lists the window's compact columns in a banded order; the principal submatrix
  * (AᵀA)_WW = A_WᵀA_W (the other columns held fixed) is factored and E[j] = sqrt(((AᵀA)_WW⁻¹)_jj)

@@ -887,6 +887,26 @@ int lsq_cov_band(lsq_handle* h, const int32_t* perm, double* E, int64_t n_ops, c
     });
 }
 
+int lsq_cov_band_bordered(lsq_handle* h, const int32_t* perm, int64_t n_border, double* E, int64_t n_ops,
+                          const int64_t* op_ptr, const int32_t* op_col, const double* op_val, double* op_err,
+                          int64_t* info) {
+    return guarded(h, [&](lsq::System& S) {
+        if (!S.G.rp.p) return fail(S, "lsq_cov_band_bordered: no matrix");
+        if (S.dist) return fail(S, "lsq_cov_band_bordered: not available on distributed handles");
+        if (!E) return fail(S, "lsq_cov_band_bordered: null output");
+        if (n_ops < 0 || (n_ops > 0 && (!op_ptr || !op_err || (op_ptr[n_ops] > 0 && (!op_col || !op_val)))))
+            return fail(S, "lsq_cov_band_bordered: bad op rows");
+        if (n_border == 0) {   // no border: the band path itself, bit for bit
+            lsq::band_cov(S, perm, -1, E, n_ops, op_ptr, op_col, op_val, op_err, info);
+            if (info) info[6] = info[7] = info[8] = info[9] = 0;
+            return 0;
+        }
+        if (!perm) return fail(S, "lsq_cov_band_bordered: a border needs perm");
+        lsq::band_cov_bordered(S, perm, n_border, E, n_ops, op_ptr, op_col, op_val, op_err, info);
+        return 0;
+    });
+}
+
 int lsq_cov_band_window(lsq_handle* h, const int32_t* perm, int64_t n_win, const uint8_t* inner, double* E,
                         int64_t n_ops, const int64_t* op_ptr, const int32_t* op_col, const double* op_val,
                         double* op_err, int64_t* info) {

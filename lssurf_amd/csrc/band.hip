@@ -1853,4 +1853,6 @@ void band_cov_windows(System& S, int64_t nwin, const int64_t* win_ptr, const int
     }
 }
 
+#include "border.inc"
+
 }  // namespace lsq

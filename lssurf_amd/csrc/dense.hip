@@ -369,4 +369,10 @@ void dense_rowrss(System& S, double* dE) {
     KERNEL_CHECK();
 }
 
+// the same for any row-major upper-triangular inverse on the device (the border block of band.hip)
+void dense_rowrss_of(const double* Ri, int64_t n, int64_t ld, double* dE, hipStream_t st) {
+    hipLaunchKernelGGL(k_rowrss_dense, dim3((unsigned)((n + 3) / 4)), dim3(BLOCK), 0, st, Ri, n, ld, dE);
+    KERNEL_CHECK();
+}
+
 }  // namespace lsq

@@ -705,6 +705,9 @@ void band_factor_download(System& S, const int32_t* perm, int64_t* info, double*
 // tiles are swept (E 0 elsewhere).  nw < 0: E over every compact column.
 void band_cov(System& S, const int32_t* perm, int64_t nw, double* E, int64_t nops, const int64_t* rp, const int32_t* ci,
               const double* v, double* op_err, int64_t* info, const uint8_t* inner = nullptr);
+// the last nbord ≥ 1 entries of perm are a dense border behind the band (border.inc, lsq_cov_band_bordered)
+void band_cov_bordered(System& S, const int32_t* perm, int64_t nbord, double* E, int64_t nops, const int64_t* rp,
+                       const int32_t* ci, const double* v, double* op_err, int64_t* info);
 // many windows, pipelined over lanes (lsq_cov_band_windows)
 void band_cov_windows(System& S, int64_t nwin, const int64_t* win_ptr, const int32_t* perm, const uint8_t* inner,
                       double* E, const int64_t* win_ops, const int64_t* op_ptr, const int32_t* op_pos,
@@ -738,6 +741,7 @@ void block_factor_packed(int64_t nb, const int64_t* ptr, int kmax, double* Ri, l
 void dense_factor(System& S);                     // R, R⁻¹ of diag(rs)·G (throws if not SPD)
 void dense_rowrss(System& S, double* dE);         // sqrt(row sums of R⁻¹²) = sqrt(diag((AᵀA)⁻¹))
 void dense_spd_factor(double* Nm, double* Ri, int64_t npad, int* err, hipStream_t st);   // multigrid coarsest
+void dense_rowrss_of(const double* Ri, int64_t n, int64_t ld, double* dE, hipStream_t st);   // sqrt(row sums of Ri²)
 
 // multigrid test hooks (mg.inc; lsq_mg_info / lsq_mg_apply)
 int mg_info(System& S, int64_t* out, int64_t cap);

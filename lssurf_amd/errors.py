@@ -25,6 +25,11 @@ held fixed differs from the marginal one by the correlations across the margin. 
 its band on the device (lsq_cov_band_window); the averaging operators' rows go with the tile of
 their support's centre (their support must lie inside the window).  Accuracy against the full
 band factor: DESIGN.md §Error propagation (tests/test_gpu_errors_window.py).
+
+With data or slope biases (a non-empty bias_model) the bias columns couple every node their tracks
+cross: 'band' orders them last (`bordered_band_order`) as the dense border of
+`lsq_cov_band_bordered` (csrc/border.inc), 'dense' takes them as ordinary columns, 'window' has no
+place for them and is refused; E gains sigma_bias / sigma_slope_bias (smooth_fit.py:274).
 """
 import os
 from time import time
@@ -53,6 +58,18 @@ def band_order(grids, keep_cols):
         key[3, idx] = sub[2] if g.N_dims > 2 else -1
     k = key[:, keep_cols]
     return np.lexsort((k[3], k[2], k[1], k[0])).astype(np.int32)
+
+
+def bordered_band_order(grids, keep_cols, n_grid):
+    """(perm, n_border) for lsq_cov_band_bordered: the kept columns of the grids (full column below
+    n_grid) in `band_order`'s order, then every kept column at or beyond n_grid — the data and slope
+    biases, which couple every node their tracks cross — ascending, as the border."""
+    keep_cols = np.asarray(keep_cols)
+    inside = np.flatnonzero(keep_cols < n_grid)
+    border = np.flatnonzero(keep_cols >= n_grid)
+    border = border[np.argsort(keep_cols[border], kind='stable')]
+    band = inside[band_order(grids, keep_cols[inside])]
+    return np.concatenate((band, border)).astype(np.int32), int(border.size)
 
 
 WINDOW_MIN_COLS = 250_000      # 'auto': the full band below, tiled windows above
@@ -243,9 +260,22 @@ def _grid_values(op, vals):
     return E[grid.col_0:grid.col_N].reshape(grid.shape)
 
 
+WINDOW_BORDER_REFUSAL = ("compute_E with bias_params: lsq_E_method='window' has no place for a bias column — a "
+                         "conditional-variance window holds the columns outside it fixed, and a bias column couples "
+                         "the whole tile; use 'band' (at most WINDOW_MIN_COLS columns) or 'dense'")
+
+
 def calc_and_parse_errors(E, G_data, Gc, Ed, Ec, data, in_TSE, keep_cols, grids, avg_ops, device=0, timing=None,
-                          method='auto'):
+                          method='auto', bias_model=None, bias_params=None):
+    """With a non-empty bias_model the system holds the bias (and slope-bias) columns behind the
+    grids': 'band' takes them as the border of lsq_cov_band_bordered, 'dense' as ordinary columns,
+    and E gains sigma_bias / sigma_slope_bias (smooth_fit.py:274)."""
     timing = {} if timing is None else timing
+    if bias_model:
+        if method == 'auto' and keep_cols.size > WINDOW_MIN_COLS:
+            method = 'window'
+        if method == 'window':
+            raise NotImplementedError('calc_and_parse_errors: ' + WINDOW_BORDER_REFUSAL)
     tic = time()
     approx = None   # window method: how σ was approximated (attached to the output grids)
     sigma_data = np.sqrt(Ed ** 2 + data.sigma_extra ** 2)
@@ -288,10 +318,17 @@ def calc_and_parse_errors(E, G_data, Gc, Ed, Ec, data, in_TSE, keep_cols, grids,
             keys = list(avg_ops)
             mats = [_compact_rows(avg_ops[k], keep_cols, Gc.col_N) for k in keys]
             op = sp.vstack(mats).tocsr() if mats else None
-            E0c, errs, info = fs.solver.cov_band(band_order(grids, keep_cols), op)
+            if bias_model:
+                n_grid = max(int(g.col_N) for g in grids.values() if getattr(g, 'N_dims', 0) >= 2)
+                perm, n_border = bordered_band_order(grids, keep_cols, n_grid)
+                E0c, errs, info = fs.solver.cov_band_bordered(perm, n_border, op)
+            else:
+                E0c, errs, info = fs.solver.cov_band(band_order(grids, keep_cols), op)
             timing['decompose_qz'] = time() - tic
             timing['E_band'] = {'tiles': int(info[0]), 'tile_rows': int(info[1]), 'bytes': int(info[2]),
                                 'tile_products': int(info[3])}
+            if bias_model:
+                timing['E_band'].update(border=n_border, border_bytes=int(info[7]), border_us=int(info[8]))
             off = 0
             for k, m in zip(keys, mats):
                 op_err[k] = errs[off:off + m.shape[0]]
@@ -327,4 +364,8 @@ def calc_and_parse_errors(E, G_data, Gc, Ed, Ec, data, in_TSE, keep_cols, grids,
     if approx is not None:   # every output grid says it is the windowed (conditional) variance
         for v in E.values():
             v.approximate = approx
+    if bias_model:   # the biases' σ, laid out as m['bias'] / m['slope_bias'] (smooth_fit.py:274)
+        from .bias_functions import parse_biases
+        E['sigma_bias'], E['sigma_slope_bias'] = parse_biases(E0, bias_model, bias_params,
+                                                              data=data if 'z_est' in data.fields else None)
     return E

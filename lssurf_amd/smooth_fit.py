@@ -26,6 +26,10 @@ bias_params, data_slope_sensors or priors), 'columns' or 'auto'.
 Data biases (bias_params) run when the solver key lsq_bias says how: 'eliminate' (the device
 eliminates them inside CGNR, lsq_set_data_bias), 'columns' (ordinary columns of a generic system)
 or 'auto' (with priors: 'columns', with a warning where it would have eliminated).
+compute_E with bias_params (and data_slope_sensors) runs when lsq_E_border=True: the bias columns are
+the dense border of a bordered band factor (lsq_cov_band_bordered) and E gains sigma_bias /
+sigma_slope_bias; without the key it raises NotImplementedError, as do lsq_E_method='window', sensor
+bias grids, priors and n_gpus > 1 with it.
 """
 from time import ctime, time
 
@@ -71,7 +75,7 @@ DEFAULTS = {'reference_epoch': 0, 'W_ctr': 1e4, 'return_fit_objects': False, 'ma
             'lsq_bias': None,
             # priors (prior_args / prior_edge_args) inside the multigrid preconditioner: their rows
             # lumped into its coarse levels (opt-in; without priors the key does nothing)
-            'lsq_prior_mg': False}
+            'lsq_prior_mg': False, 'lsq_E_border': False}
 
 OUT_OF_SCOPE = ('lagrangian_coords', 'constraint_scaling_maps', 'mask_file', 'bias_edit_vals')
 
@@ -772,6 +776,8 @@ def smooth_fit(**kwargs):
                              "back through them)")
     if not isinstance(args['lsq_prior_mg'], (bool, np.bool_)):
         raise ValueError(f"smooth_fit: lsq_prior_mg must be True or False, not {args['lsq_prior_mg']!r}")
+    if not isinstance(args['lsq_E_border'], (bool, np.bool_)):
+        raise ValueError(f"smooth_fit: lsq_E_border must be True or False, not {args['lsq_E_border']!r}")
     bias_mode = args['lsq_bias']
     if args['bias_params'] is not None:
         if bias_mode is None:
@@ -779,8 +785,11 @@ def smooth_fit(**kwargs):
                                       "'columns' or 'auto'); without it data biases are outside lssurf_amd")
         if bias_mode not in ('eliminate', 'columns', 'auto'):
             raise ValueError(f"smooth_fit: lsq_bias must be 'eliminate', 'columns' or 'auto', not {bias_mode!r}")
-        if args['compute_E']:
+        if args['compute_E'] and not args['lsq_E_border']:
             raise NotImplementedError("smooth_fit: compute_E with bias_params (sigma_bias) is outside lssurf_amd")
+        if args['compute_E'] and args['lsq_E_method'] == 'window':
+            from .errors import WINDOW_BORDER_REFUSAL
+            raise NotImplementedError('smooth_fit: ' + WINDOW_BORDER_REFUSAL)
         if int(args['n_gpus']) > 1 or (args['devices'] is not None and len(args['devices']) > 1):
             raise NotImplementedError("smooth_fit: bias_params runs on one GPU")
         if bias_mode == 'eliminate' and args['lsq_method'] == 'lsqr':
@@ -1058,7 +1067,8 @@ def smooth_fit(**kwargs):
                 print('Starting uncertainty calculation', flush=True)
                 tic_error = time()
             calc_and_parse_errors(E, G_data, Gc, Ed, Ec(), data, in_TSE, keep_cols, grids, averaging_ops,
-                                  device=args['device'], timing=timing, method=args['lsq_E_method'])
+                                  device=args['device'], timing=timing, method=args['lsq_E_method'],
+                                  bias_model=bias_model, bias_params=args['bias_params'])
             if args['VERBOSE']:
                 print('\tUncertainty propagation took %3.2f seconds' % (time() - tic_error), flush=True)
     finally:

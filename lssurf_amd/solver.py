@@ -461,6 +461,29 @@ class LSQSolver:
                                          ptr(rp), ptr(ci), ptr(v), ptr(out), ptr(info)), 'lsq_cov_band')
         return E, out, info
 
+    def cov_band_bordered(self, perm, n_border, op=None):
+        """cov_band for a banded system with a dense border (lsq_cov_band_bordered): the first
+        n − n_border entries of `perm` are the band columns in a banded order, the last n_border
+        the border columns (smooth_fit's bias and slope-bias columns; at most LSQ_BORDER_MAX).
+        E per compact column; the rows of `op` must hold band columns only.  info: 10 entries
+        (include/lsqsurf.h).  n_border = 0 is cov_band(perm)."""
+        E = np.zeros(self.n)
+        info = np.zeros(10, np.int64)
+        pp = as_c(perm, np.int32)
+        if pp.size != self.n:
+            raise ValueError('cov_band_bordered: perm must have one entry per column')
+        if op is None:
+            self._check(self._L.lsq_cov_band_bordered(self._h, ptr(pp), int(n_border), ptr(E), 0, None, None, None,
+                                                      None, ptr(info)), 'lsq_cov_band_bordered')
+            return E, None, info
+        op = sp.csr_matrix(op)
+        op.sort_indices()
+        rp, ci, v = as_c(op.indptr, np.int64), as_c(op.indices, np.int32), as_c(op.data, np.float64)
+        out = np.zeros(op.shape[0])
+        self._check(self._L.lsq_cov_band_bordered(self._h, ptr(pp), int(n_border), ptr(E), op.shape[0], ptr(rp),
+                                                  ptr(ci), ptr(v), ptr(out), ptr(info)), 'lsq_cov_band_bordered')
+        return E, out, info
+
     def cov_band_window(self, perm_w, op=None, inner=None):
         """cov_band for a window W of the columns (perm_w: its compact columns in a banded order):
         E[j] = sqrt(((A_WᵀA_W)⁻¹)_jj) in WINDOW order (len(perm_w) entries) and the op rows' errors,
