@@ -591,6 +591,34 @@ int lsq_set_sensor_grids(lsq_handle* h, int64_t npts, const int32_t* grid /* −
                          int32_t ng, const int64_t* n_nodes, const int64_t* k_ptr, const int32_t* k_row,
                          const int32_t* k_col, const double* k_val);
 int lsq_get_sensor_grids(lsq_handle* h, double* a);
+/* Sensor grids beside data biases and slopes.  The arguments of lsq_set_sensor_grids; call it after
+ * lsq_set_matrix_stencil and after any lsq_set_data_bias / lsq_set_data_slope, whose layout it reads
+ * from the handle.  With Z = [B_bias U_slope B_grid] and M = ZᵀW²Z + C the eliminated block stays block
+ * diagonal when every bias ID and every slope group lies inside one grid's rows or outside every grid:
+ *   - a bias ID with a row in a grid must have all its rows in that grid; the grid's block claims it as
+ *     a dense node (coefficient 1 on its rows, c_j² on the diagonal);
+ *   - a slope group with a row (grp ≥ 0) in a grid must have all of them in that grid; it is claimed as
+ *     two dense nodes (coefficients u, c² on the diagonal);
+ *   - the other IDs and groups stay on the bias / slope path, which the rows of every grid leave.
+ * The two parts touch disjoint rows and their corrections add.  Returns −2 with the handle unchanged on
+ * everything lsq_set_sensor_grids refuses except biases or slopes being set, on an ID or group that is
+ * not nested in this sense, on more than LSQ_SGRID_MAX_DENSE dense nodes in one grid, on lattice plus
+ * dense nodes over LSQ_SGRID_MAX_NODES, or on inverse factors (counted with the dense nodes) over
+ * LSQ_SGRID_MAX_FACTOR_BYTES.  lsq_set_data_bias and lsq_set_data_slope go on returning −2 while grids
+ * are set, their clearing forms (nb = 0, ng = 0) included: the blocks hold the claimed IDs and groups; ng = 0 (through either call) clears the grids, and the handle then solves with its biases
+ * and slopes bit for bit as if no grid had been set.  Without biases and slopes the call sets exactly
+ * what lsq_set_sensor_grids sets.  lsq_get_data_bias and lsq_get_data_slope return every bias and slope
+ * of the last solve's x, the claimed ones from their block's solution; lsq_get_sensor_grids returns the
+ * lattice nodes only.  The solve rules, lsq_normal_apply, the warm start and lsq_profile_sensor_grids
+ * hold as for either part alone.  The step launches the bias path's sums, the blocks' three reduce
+ * launches, the bias path's apply pass and the blocks' apply pass: lsq_profile_sensor_grids' first stage
+ * then spans the bias path's sums and its fourth the bias path's apply pass as well, and
+ * lsq_profile_data_slope's fourth stage spans the blocks' three reduce launches.
+ * Every sum runs in a fixed order without atomics. */
+#define LSQ_SGRID_MAX_DENSE 16
+int lsq_set_sensor_grids_joint(lsq_handle* h, int64_t npts, const int32_t* grid, const int32_t* node,
+                               const double* wt, int32_t ng, const int64_t* n_nodes, const int64_t* k_ptr,
+                               const int32_t* k_row, const int32_t* k_col, const double* k_val);
 /* The sensor grids' kernels timed inside reps real iterations of the live lsq_iterate state (method 1,
  * this precond; HIP events between the launches): out8 = {ms of s = Bᵀ td, of z = R⁻ᵀ s, of y = R⁻¹ z,
  * of the apply pass, and the algorithmic HBM bytes of each}.  −2 without such a state or without grids

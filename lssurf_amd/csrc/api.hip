@@ -27,7 +27,7 @@ void slope_get(System& S, double* h_g);
 void cg_profile_slope(System& S, int reps, int precond, double* out8);
 void sgrid_set(System& S, int64_t npts, const int32_t* h_grid, const int32_t* h_node, const double* h_wt, int64_t ng,
                const int64_t* h_nn, const int64_t* k_ptr, const int32_t* k_row, const int32_t* k_col,
-               const double* k_val);
+               const double* k_val, bool joint);
 void sgrid_clear(System& S);
 void sgrid_get(System& S, double* h_a);
 void cg_profile_sgrid(System& S, int reps, int precond, double* out8);
@@ -574,6 +574,8 @@ int lsq_set_data_bias(lsq_handle* h, int64_t npts, const int32_t* id, int64_t nb
         if (!S.G.rp.p) return fail(S, "lsq_set_data_bias: no matrix");
         if (nb < 0 || npts < 0) return fail(S, "lsq_set_data_bias: bad sizes");
         if (nb == 0 || !id || !c) {
+            // joint grids hold the biases' layout (claimed IDs, the sink): clearing is refused like setting
+            if (S.sgrid.ng) return fail(S, "lsq_set_data_bias: sensor grids are set (lsq_set_sensor_grids); clear them first");
             lsq::bias_clear(S);
             return 0;
         }
@@ -595,6 +597,7 @@ int lsq_set_data_slope(lsq_handle* h, int64_t npts, const int32_t* grp, const do
         if (!S.G.rp.p) return fail(S, "lsq_set_data_slope: no matrix");
         if (ng < 0 || npts < 0) return fail(S, "lsq_set_data_slope: bad sizes");
         if (ng == 0 || !grp || !u || !c) {
+            if (S.sgrid.ng) return fail(S, "lsq_set_data_slope: sensor grids are set (lsq_set_sensor_grids); clear them first");
             lsq::slope_clear(S);
             return 0;
         }
@@ -632,7 +635,23 @@ int lsq_set_sensor_grids(lsq_handle* h, int64_t npts, const int32_t* grid, const
             return 0;
         }
         if (k_ptr && k_ptr[ng] > 0 && (!k_row || !k_col || !k_val)) return fail(S, "lsq_set_sensor_grids: K's arrays are null");
-        lsq::sgrid_set(S, npts, grid, node, wt, ng, n_nodes, k_ptr, k_row, k_col, k_val);
+        lsq::sgrid_set(S, npts, grid, node, wt, ng, n_nodes, k_ptr, k_row, k_col, k_val, false);
+        return 0;
+    });
+}
+
+int lsq_set_sensor_grids_joint(lsq_handle* h, int64_t npts, const int32_t* grid, const int32_t* node, const double* wt,
+                               int32_t ng, const int64_t* n_nodes, const int64_t* k_ptr, const int32_t* k_row,
+                               const int32_t* k_col, const double* k_val) {
+    return guarded(h, [&](lsq::System& S) {
+        if (!S.G.rp.p) return fail(S, "lsq_set_sensor_grids_joint: no matrix");
+        if (ng < 0 || npts < 0) return fail(S, "lsq_set_sensor_grids_joint: bad sizes");
+        if (ng == 0 || !grid || !node || !wt || !n_nodes) {
+            lsq::sgrid_clear(S);
+            return 0;
+        }
+        if (k_ptr && k_ptr[ng] > 0 && (!k_row || !k_col || !k_val)) return fail(S, "lsq_set_sensor_grids_joint: K's arrays are null");
+        lsq::sgrid_set(S, npts, grid, node, wt, ng, n_nodes, k_ptr, k_row, k_col, k_val, true);
         return 0;
     });
 }

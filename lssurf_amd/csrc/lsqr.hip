@@ -28,7 +28,8 @@ namespace {
 
 constexpr int NPART = 2048;   // partial-sum slots per reduction (fixed grid => deterministic)
 constexpr int BIAS_NPART = 64;   // further slots behind them: the data-bias elimination's partials (bias.inc)
-constexpr int XR_NPART = 512;    // and behind those: the extra rows' partials (xrows.inc)
+constexpr int ELIM_NPART = 2 * BIAS_NPART;   // room for two eliminations side by side (biases / slopes and joint sensor grids)
+constexpr int XR_NPART = 512;   // and behind those: the extra rows' partials (xrows.inc)
 
 // ---- SELL-64 row kernel body: one lane = one row, 4 entries in flight per step -------------
 __device__ __forceinline__ double sell_row_dot(const int32_t* __restrict__ ci, const double* __restrict__ val,
@@ -438,18 +439,18 @@ void ensure_workspace(System& S) {
         S.tt.alloc(n);
     }
     if (!S.part_u.p) {
-        S.part_u.alloc(NPART + BIAS_NPART);
+        S.part_u.alloc(NPART + ELIM_NPART);
         S.part_v.alloc(NPART);
         S.part_w.alloc(NPART);
-        S.part_b.alloc(NPART + BIAS_NPART);
+        S.part_b.alloc(NPART + ELIM_NPART);
         S.st.alloc(1);
     }
     // extra rows set (xrows.inc): room for their partials behind the others; without them every
     // buffer keeps the size it always had
-    if (S.xr.on && S.part_u.n < NPART + BIAS_NPART + XR_NPART) {
+    if (S.xr.on && S.part_u.n < NPART + ELIM_NPART + XR_NPART) {
         graph_cache_drop(&S);
-        S.part_u.alloc(NPART + BIAS_NPART + XR_NPART);
-        S.part_b.alloc(NPART + BIAS_NPART + XR_NPART);
+        S.part_u.alloc(NPART + ELIM_NPART + XR_NPART);
+        S.part_b.alloc(NPART + ELIM_NPART + XR_NPART);
     }
 }
 

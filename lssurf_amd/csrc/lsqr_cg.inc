@@ -1879,10 +1879,10 @@ void cg_workspace(System& S) {
     if (S.cg_part_g.n != npg) S.cg_part_g.alloc(npg);
     if (!S.cg_part_r.p) S.cg_part_r.alloc(NPART);
     // the data rows' partials, then the biases'; then (set: more room) the extra rows'
-    if (!S.cg_part_t.p) S.cg_part_t.alloc(NPART + BIAS_NPART);
-    if (S.xr.on && S.cg_part_t.n < NPART + BIAS_NPART + XR_NPART) {
+    if (!S.cg_part_t.p) S.cg_part_t.alloc(NPART + ELIM_NPART);
+    if (S.xr.on && S.cg_part_t.n < NPART + ELIM_NPART + XR_NPART) {
         graph_cache_drop(&S);
-        S.cg_part_t.alloc(NPART + BIAS_NPART + XR_NPART);
+        S.cg_part_t.alloc(NPART + ELIM_NPART + XR_NPART);
     }
     if (!S.cst.p) S.cst.alloc(1);
     if (!S.side) {
@@ -1991,6 +1991,7 @@ constexpr unsigned cg_bit(int stage) { return 1u << stage; }
 // for every repetition; stage names the ones recorded so far).  The solver passes no marks.
 struct CgMarks {
     unsigned mask = 0;
+    bool bias_path = false;   // both eliminations in the step: E0 … E3 stand on the bias / slope path, not on the grids'
     std::vector<hipEvent_t> ev;
     std::vector<int> stage;
 };
@@ -2515,10 +2516,12 @@ static void cg_need_live(const System& S, int precond, const char* who) {
 // an event behind every stage of mask, so every kernel sees the caches its predecessors leave
 // behind.  ms[s] = the mean time from the step's previous mark to the one behind stage s (0 for a
 // stage that is not in mask, did not run, or carries the step's first mark).
-static void cg_profile_steps(System& S, int reps, int precond, unsigned mask, double ms[CG_NSTAGE]) {
+static void cg_profile_steps(System& S, int reps, int precond, unsigned mask, double ms[CG_NSTAGE],
+                             bool bias_path = false) {
     const CgGrids g = cg_grids(S, precond);
     CgMarks m;
     m.mask = mask;
+    m.bias_path = bias_path;
     m.ev.resize((size_t)reps * __builtin_popcount(mask));
     for (auto& e : m.ev) HIP_CHECK(hipEventCreate(&e));
     for (int r = 0; r < reps; ++r) {
@@ -2618,10 +2621,10 @@ void cg_profile_xr(System& S, int reps, int precond, double* out) {
 }
 
 // the elimination's four kernels inside real iterations: out4 = ms of the stages E0 … E3
-static void cg_profile_elim(System& S, int reps, int precond, double* out) {
+static void cg_profile_elim(System& S, int reps, int precond, double* out, bool bias_path = false) {
     double ms[CG_NSTAGE];
     cg_profile_steps(S, reps, precond,
-                     cg_bit(CG_AD) | cg_bit(CG_E0) | cg_bit(CG_E1) | cg_bit(CG_E2) | cg_bit(CG_E3), ms);
+                     cg_bit(CG_AD) | cg_bit(CG_E0) | cg_bit(CG_E1) | cg_bit(CG_E2) | cg_bit(CG_E3), ms, bias_path);
     std::copy(ms + CG_E0, ms + CG_E3 + 1, out);
 }
 
@@ -2631,7 +2634,7 @@ static void cg_profile_elim(System& S, int reps, int precond, double* out) {
 void cg_profile_slope(System& S, int reps, int precond, double* out) {
     cg_need_live(S, precond, "lsq_profile_data_slope");
     if (!bias_active(S) || !S.bias.ng) throw std::invalid_argument("lsq_profile_data_slope: no slopes in the CGNR operator");
-    cg_profile_elim(S, reps, precond, out);
+    cg_profile_elim(S, reps, precond, out, true);   // beside joint sensor grids: the marks on this path (elim_launch_step)
     slope_kernel_bytes(S, out + 4);
 }
 
@@ -2732,30 +2735,46 @@ namespace {
 // The layout of the eliminated columns.  h_id: the data rows' bias IDs in the caller's row order
 // (null: no biases, the slopes' pseudo-IDs), h_c: 1 / E_bias per ID; h_grp (null: no slopes), h_u,
 // h_gc: the rows' slope groups, their coefficients and the groups' c.  Arguments are valid.
+// h_sink (null: none): the rows that leave this path for a sensor grid's block (BiasData::sink); they
+// form one last ID outside every group with c² = +∞.  Without such a row the layout is the one made
+// without h_sink.
 void bias_build(System& S, int64_t npts, const int32_t* h_id, int64_t nb, const double* h_c, const int32_t* h_grp,
-                const double* h_u, int64_t ng, const double* h_gc) {
+                const double* h_u, int64_t ng, const double* h_gc, const uint8_t* h_sink = nullptr) {
     std::vector<int32_t> perm(std::max<int64_t>(npts, 1));
     S.dmf_perm.download(perm.data(), npts, S.stream);
     HIP_CHECK(hipStreamSynchronize(S.stream));
     std::vector<int32_t> keep_id, keep_grp;   // the caller's arrays outlive the previous layout
-    std::vector<double> keep_c;
+    std::vector<double> keep_c, keep_u, keep_gc;
+    std::vector<uint8_t> keep_sink;
     if (h_id) {
         keep_id.assign(h_id, h_id + npts);
         keep_c.assign(h_c, h_c + nb);
     }
-    if (h_grp) keep_grp.assign(h_grp, h_grp + npts);
+    if (h_grp) {
+        keep_grp.assign(h_grp, h_grp + npts);
+        keep_u.assign(h_u, h_u + 2 * npts);
+        keep_gc.assign(h_gc, h_gc + 2 * ng);
+    }
+    bool has_sink = false;
+    for (int64_t i = 0; h_sink && i < npts; ++i) has_sink = has_sink || h_sink[i];
+    if (has_sink) keep_sink.assign(h_sink, h_sink + npts);
     bias_clear(S);
     graph_cache_drop(&S);   // captured iterations hold no elimination step yet
     S.cg_ready = false;
     const bool pseudo = !h_id;
-    const int64_t ne = pseudo ? ng + 1 : nb;   // IDs, or one pseudo-ID per group and one for the rows outside
-    auto eid = [&](int64_t i) -> int32_t { return pseudo ? (h_grp[i] < 0 ? (int32_t)ng : h_grp[i]) : h_id[i]; };
+    const int64_t ne0 = pseudo ? ng + 1 : nb;   // IDs, or one pseudo-ID per group and one for the rows outside
+    const int64_t ne = ne0 + (has_sink ? 1 : 0);   // and the sink
+    auto sunk = [&](int64_t i) -> bool { return has_sink && keep_sink[i]; };
+    auto eid = [&](int64_t i) -> int32_t {
+        if (sunk(i)) return (int32_t)ne0;
+        return pseudo ? (h_grp[i] < 0 ? (int32_t)ng : h_grp[i]) : h_id[i];
+    };
     // ranks: the IDs that carry points, in ID order; slopes set: by (group, ID), the IDs outside every
     // group last.  The sorted points are indexed stably by rank.
     std::vector<int32_t> cnt(ne + 1, 0), rank_of(ne, -1), rank_id, sgrp(h_grp ? ne : 0, -1);
     for (int64_t i = 0; i < npts; ++i) {
         ++cnt[eid(i)];
-        if (h_grp && h_grp[i] >= 0) sgrp[eid(i)] = h_grp[i];
+        if (h_grp && h_grp[i] >= 0 && !sunk(i)) sgrp[eid(i)] = h_grp[i];
     }
     for (int64_t j = 0; j < ne; ++j)
         if (cnt[j]) rank_id.push_back((int32_t)j);
@@ -2781,7 +2800,10 @@ void bias_build(System& S, int64_t npts, const int32_t* h_id, int64_t nb, const 
     for (int64_t r = 0; r < ns; ++r) {
         seg[r + 1] = seg[r] + cnt[rank_id[r]];
         pos[r] = seg[r];
-        c2[r] = pseudo ? 0.0 : h_c[rank_id[r]] * h_c[rank_id[r]];
+        if (rank_id[r] == ne0)
+            c2[r] = INFINITY;   // the sink: D = +∞
+        else
+            c2[r] = pseudo ? 0.0 : h_c[rank_id[r]] * h_c[rank_id[r]];
     }
     for (int64_t i = 0; i < npts; ++i) {
         const int32_t r = rank_of[eid(perm[i])];
@@ -2834,7 +2856,7 @@ void bias_build(System& S, int64_t npts, const int32_t* h_id, int64_t nb, const 
     B.D.alloc(std::max<int64_t>(ns, 1));
     B.sD.alloc(std::max<int64_t>(ns, 1));
     B.slots.alloc(std::max<int64_t>(nslots, 1) * nch);
-    B.bval.alloc(std::max<int64_t>(nb, 1));
+    B.bval.alloc(nb + 1);   // the sink's rank scatters its 0 behind the IDs
     std::vector<double> u, gc2;
     if (h_grp) {
         B.ng = ng; B.nsr = nsr; B.npts3 = npts3; B.nslots3 = nslots3; B.pseudo = pseudo;
@@ -2843,7 +2865,7 @@ void bias_build(System& S, int64_t npts, const int32_t* h_id, int64_t nb, const 
         B.nbk = B.nrk + B.ngk;
         u.assign(2 * std::max<int64_t>(npts, 1), 0.0);
         for (int64_t i = 0; i < npts; ++i)
-            if (h_grp[perm[i]] >= 0) {
+            if (h_grp[perm[i]] >= 0 && !sunk(perm[i])) {
                 u[2 * i] = h_u[2 * (int64_t)perm[i]];
                 u[2 * i + 1] = h_u[2 * (int64_t)perm[i] + 1];
             }
@@ -2861,6 +2883,10 @@ void bias_build(System& S, int64_t npts, const int32_t* h_id, int64_t nb, const 
     B.h_id = std::move(keep_id);
     B.h_c = std::move(keep_c);
     B.h_grp = std::move(keep_grp);
+    B.h_u = std::move(keep_u);
+    B.h_gc = std::move(keep_gc);
+    B.h_sink = std::move(keep_sink);
+    B.sink = has_sink;
     B.on = npts > 0 && ns > 0;   // no data rows: every bias is 0, the operator is unchanged
 }
 }  // namespace
@@ -2980,30 +3006,86 @@ void slope_get(System& S, double* h_g) {
     HIP_CHECK(hipStreamSynchronize(S.stream));
 }
 
+// the layout of the biases and slopes that are set, built again with the rows of h_sink (null: none)
+// taken out: without a sink bit for bit the layout lsq_set_data_bias / lsq_set_data_slope made
+static void bias_rebuild(System& S, const uint8_t* h_sink) {
+    const BiasData& B = S.bias;
+    const std::vector<int32_t> id = B.h_id, grp = B.h_grp;
+    const std::vector<double> c = B.h_c, u = B.h_u, gc = B.h_gc;
+    const int64_t nb = B.nb, ng = B.ng, npts = (int64_t)(nb ? id.size() : grp.size());
+    bias_build(S, npts, nb ? id.data() : nullptr, nb, nb ? c.data() : nullptr, ng ? grp.data() : nullptr,
+               ng ? u.data() : nullptr, ng, ng ? gc.data() : nullptr, h_sink);
+}
+
 // ---- sensor bias grids (sgrid.inc): set, clear, read back ----------------------------------------
 void sgrid_clear(System& S) {
     if (!S.sgrid.ng) return;
     graph_cache_drop(&S);   // captured iterations hold the step's launches
     S.sgrid = SgridData{};
     S.cg_ready = false;
+    if (S.bias.sink) bias_rebuild(S, nullptr);   // the grids' rows return to the bias / slope path
 }
 
 // grid: the data rows' grids (−1: none) in the caller's row order; node, wt: four local nodes and
 // weights per row; n_nodes per grid; K_s as triplets k_ptr[s] … k_ptr[s + 1] with local rows and columns.
 // Every check runs before anything of the handle changes.
+//
+// joint (lsq_set_sensor_grids_joint): biases and slopes may be set.  A bias ID or a slope group with a
+// row in a grid must have all its rows in that grid ("nested") and becomes a dense node of the grid's
+// block (SgridData); the rows of every grid leave the bias / slope path (BiasData::sink).
 void sgrid_set(System& S, int64_t npts, const int32_t* h_grid, const int32_t* h_node, const double* h_wt, int64_t ng,
                const int64_t* h_nn, const int64_t* k_ptr, const int32_t* k_row, const int32_t* k_col,
-               const double* k_val) {
+               const double* k_val, bool joint) {
     if (!S.mf || S.dist) throw std::invalid_argument("lsq_set_sensor_grids: needs a single-GPU structured system (lsq_set_matrix_stencil)");
-    if (S.bias.nb || S.bias.ng) throw std::invalid_argument("lsq_set_sensor_grids: data biases or slopes are set; the joint block is not one matrix per grid");
+    if (!joint && (S.bias.nb || S.bias.ng)) throw std::invalid_argument("lsq_set_sensor_grids: data biases or slopes are set; the joint block is not one matrix per grid");
     if (npts != S.mfh.npts) throw std::invalid_argument("lsq_set_sensor_grids: npts differs from the system's data rows");
     if (!S.dmf.ok || S.dmf.npts != npts)
         throw std::invalid_argument("lsq_set_sensor_grids: needs matrix-free data rows (interpolation grids on one (y, x) lattice)");
-    std::vector<int64_t> nn(h_nn, h_nn + ng), npad(ng), poff(ng + 1, 0), moff(ng + 1, 0);
-    for (int64_t g = 0; g < ng; ++g) {
-        if (nn[g] < 1 || nn[g] > SG_MAX_NODES)
-            throw std::invalid_argument("lsq_set_sensor_grids: grid " + std::to_string(g) + " has " + std::to_string(nn[g]) +
+    std::vector<int64_t> nl(h_nn, h_nn + ng), nx(ng, 0), npad(ng), poff(ng + 1, 0), moff(ng + 1, 0);
+    for (int64_t g = 0; g < ng; ++g)
+        if (nl[g] < 1 || nl[g] > SG_MAX_NODES)
+            throw std::invalid_argument("lsq_set_sensor_grids: grid " + std::to_string(g) + " has " + std::to_string(nl[g]) +
                                         " nodes; a grid holds 1 … " + std::to_string(SG_MAX_NODES) + " (the size cap)");
+    // the dense nodes: the bias IDs (in ID order), then the slope groups (two nodes each) of every grid
+    const bool jb = joint && S.bias.nb > 0, js = joint && S.bias.ng > 0;
+    const int64_t nb = jb ? S.bias.nb : 0, nsg = js ? S.bias.ng : 0;
+    const std::vector<int32_t>& b_id = S.bias.h_id;
+    const std::vector<int32_t>& b_grp = S.bias.h_grp;
+    std::vector<int32_t> id_grid(nb, -2), grp_grid(nsg, -2);   // −2: no row seen, −1: rows outside every grid
+    std::vector<int32_t> id_loc(nb, -1), grp_loc(nsg, -1);     // the local node of a claimed ID, of a claimed group's x slope
+    if (jb || js) {
+        auto claim = [&](int32_t& owner, int32_t g, const char* what) {
+            if (owner == -2)
+                owner = g;
+            else if (owner != g)
+                throw std::invalid_argument(std::string("lsq_set_sensor_grids_joint: the layout is not nested (the rows of a ") +
+                                            what + " lie in a grid and outside it, or in two grids)");
+        };
+        for (int64_t i = 0; i < npts; ++i) {
+            const int32_t g = h_grid[i];
+            if (g < -1 || g >= ng) throw std::invalid_argument("lsq_set_sensor_grids: a grid lies outside {-1} and [0, ng)");
+            if (jb) claim(id_grid[b_id[i]], g, "bias ID");
+            if (js && b_grp[i] >= 0) claim(grp_grid[b_grp[i]], g, "slope group");
+        }
+        for (int64_t j = 0; j < nb; ++j)
+            if (id_grid[j] >= 0) id_loc[j] = (int32_t)(nl[id_grid[j]] + nx[id_grid[j]]++);
+        for (int64_t s = 0; s < nsg; ++s)
+            if (grp_grid[s] >= 0) {
+                grp_loc[s] = (int32_t)(nl[grp_grid[s]] + nx[grp_grid[s]]);
+                nx[grp_grid[s]] += 2;
+            }
+    }
+    std::vector<int64_t> nn(ng);
+    int64_t nxt = 0;
+    for (int64_t g = 0; g < ng; ++g) {
+        if (nx[g] > SG_MAX_DENSE)
+            throw std::invalid_argument("lsq_set_sensor_grids_joint: grid " + std::to_string(g) + " has " + std::to_string(nx[g]) +
+                                        " dense nodes (bias IDs and slopes inside it); the cap is " + std::to_string(SG_MAX_DENSE));
+        nn[g] = nl[g] + nx[g];
+        nxt += nx[g];
+        if (nn[g] > SG_MAX_NODES)
+            throw std::invalid_argument("lsq_set_sensor_grids_joint: grid " + std::to_string(g) + " has " + std::to_string(nn[g]) +
+                                        " lattice and dense nodes; a block holds 1 … " + std::to_string(SG_MAX_NODES) + " (the size cap)");
         npad[g] = (nn[g] + 63) / 64 * 64;
         poff[g + 1] = poff[g] + npad[g];
         moff[g + 1] = moff[g] + npad[g] * npad[g];
@@ -3017,7 +3099,7 @@ void sgrid_set(System& S, int64_t npts, const int32_t* h_grid, const int32_t* h_
     for (int64_t g = 0; g < ng && k_ptr; ++g) {
         if (k_ptr[g + 1] < k_ptr[g]) throw std::invalid_argument("lsq_set_sensor_grids: k_ptr must not decrease");
         for (int64_t t = k_ptr[g]; t < k_ptr[g + 1]; ++t) {
-            if (k_row[t] < 0 || k_row[t] >= nn[g] || k_col[t] < 0 || k_col[t] >= nn[g])
+            if (k_row[t] < 0 || k_row[t] >= nl[g] || k_col[t] < 0 || k_col[t] >= nl[g])
                 throw std::invalid_argument("lsq_set_sensor_grids: an entry of K lies outside its grid's nodes");
             if (!std::isfinite(k_val[t])) throw std::invalid_argument("lsq_set_sensor_grids: a value of K is not finite");
             kent.emplace_back(moff[g] + (int64_t)k_row[t] * npad[g] + k_col[t], k_val[t]);
@@ -3028,7 +3110,7 @@ void sgrid_set(System& S, int64_t npts, const int32_t* h_grid, const int32_t* h_
         if (g < -1 || g >= ng) throw std::invalid_argument("lsq_set_sensor_grids: a grid lies outside {-1} and [0, ng)");
         if (g < 0) continue;
         for (int q = 0; q < 4; ++q) {
-            if (h_node[4 * i + q] < 0 || h_node[4 * i + q] >= nn[g])
+            if (h_node[4 * i + q] < 0 || h_node[4 * i + q] >= nl[g])
                 throw std::invalid_argument("lsq_set_sensor_grids: a node lies outside its grid");
             if (!std::isfinite(h_wt[4 * i + q])) throw std::invalid_argument("lsq_set_sensor_grids: a weight is not finite");
         }
@@ -3036,9 +3118,28 @@ void sgrid_set(System& S, int64_t npts, const int32_t* h_grid, const int32_t* h_
     std::vector<int32_t> perm(std::max<int64_t>(npts, 1));
     S.dmf_perm.download(perm.data(), npts, S.stream);
     HIP_CHECK(hipStreamSynchronize(S.stream));
+    // the dense nodes' c² on the diagonal, behind K's entries
+    std::vector<int32_t> cl_id, cl_id_node, cl_grp, cl_grp_node;
+    for (int64_t j = 0; j < nb; ++j)
+        if (id_loc[j] >= 0) {
+            const int64_t g = id_grid[j], d = id_loc[j];
+            kent.emplace_back(moff[g] + d * npad[g] + d, S.bias.h_c[j] * S.bias.h_c[j]);
+            cl_id.push_back((int32_t)j);
+            cl_id_node.push_back((int32_t)(poff[g] + d));
+        }
+    for (int64_t s = 0; s < nsg; ++s)
+        if (grp_loc[s] >= 0) {
+            const int64_t g = grp_grid[s];
+            for (int64_t k = 0; k < 2; ++k) {
+                const int64_t d = grp_loc[s] + k;
+                kent.emplace_back(moff[g] + d * npad[g] + d, S.bias.h_gc[2 * s + k] * S.bias.h_gc[2 * s + k]);
+            }
+            cl_grp.push_back((int32_t)s);
+            cl_grp_node.push_back((int32_t)(poff[g] + grp_loc[s]));
+        }
     // the rows that lie in a grid, in sorted point order; the transpose by padded node in that order
-    std::vector<int32_t> gp_pt, gp_node;
-    std::vector<double> gp_wt;
+    std::vector<int32_t> gp_pt, gp_node, gp_xnode;
+    std::vector<double> gp_wt, gp_xu;
     std::vector<int64_t> tr_ptr(ntp + 1, 0);
     for (int64_t i = 0; i < npts; ++i) {
         const int64_t r = perm[i];
@@ -3051,15 +3152,54 @@ void sgrid_set(System& S, int64_t npts, const int32_t* h_grid, const int32_t* h_
             gp_wt.push_back(h_wt[4 * r + q]);
             if (h_wt[4 * r + q] != 0.0) ++tr_ptr[k + 1];
         }
+        if (!nxt) continue;
+        // the row's dense entries: its ID's node, its group's two (every ID and group of a grid's row is claimed by the grid)
+        const int32_t kb = jb ? (int32_t)(poff[g] + id_loc[b_id[r]]) : -1;
+        const int32_t ks = js && b_grp[r] >= 0 ? (int32_t)(poff[g] + grp_loc[b_grp[r]]) : -1;
+        gp_xnode.insert(gp_xnode.end(), {kb, ks, ks >= 0 ? ks + 1 : -1, -1});
+        gp_xu.push_back(ks >= 0 ? S.bias.h_u[2 * r] : 0.0);
+        gp_xu.push_back(ks >= 0 ? S.bias.h_u[2 * r + 1] : 0.0);
+        if (kb >= 0) ++tr_ptr[kb + 1];
+        if (ks >= 0) {
+            ++tr_ptr[ks + 1];
+            ++tr_ptr[ks + 2];
+        }
     }
     const int64_t ngp = (int64_t)gp_pt.size();
     for (int64_t k = 0; k < ntp; ++k) tr_ptr[k + 1] += tr_ptr[k];
     const int64_t nent = tr_ptr[ntp];
     if (nent >= (int64_t)INT32_MAX) throw std::invalid_argument("lsq_set_sensor_grids: too many entries");
+    // the dense nodes' long lists in segments of SG_SEG entries (k_sg_btd_seg)
+    std::vector<int32_t> seg_ptr(ntp + 1, 0);
+    std::vector<int64_t> seg_lo, seg_hi;
+    // LSQ_SG_SEG=0 (read at set time): one wave per list, the layout tools/sgrid_joint_step.py measures against
+    const bool seg_on = !getenv("LSQ_SG_SEG") || atoi(getenv("LSQ_SG_SEG")) != 0;
+    for (int64_t g = 0; g < ng && nxt && seg_on; ++g)
+        for (int64_t d = nl[g]; d < nn[g]; ++d) {
+            const int64_t k = poff[g] + d;
+            if (tr_ptr[k + 1] - tr_ptr[k] <= SG_SEG) continue;
+            for (int64_t lo = tr_ptr[k]; lo < tr_ptr[k + 1]; lo += SG_SEG) {
+                seg_lo.push_back(lo);
+                seg_hi.push_back(std::min(lo + SG_SEG, tr_ptr[k + 1]));
+                ++seg_ptr[k + 1];
+            }
+        }
+    for (int64_t k = 0; k < ntp; ++k) seg_ptr[k + 1] += seg_ptr[k];
+    const int64_t nseg = (int64_t)seg_lo.size();
     std::vector<int32_t> tr_pt(std::max<int64_t>(nent, 1)), tr_gp(std::max<int64_t>(nent, 1)), nbr(std::max<int64_t>(ntp, 1) * SG_NBR, -1);
     std::vector<uint32_t> tr_slot(std::max<int64_t>(nent, 1));
     std::vector<double> tr_w(std::max<int64_t>(nent, 1));
     std::vector<int64_t> fill(tr_ptr.begin(), tr_ptr.end() - 1);
+    for (int64_t j = 0; j < ngp && nxt; ++j)   // the dense nodes' lists: every row of the ID or group, in point order
+        for (int q = 0; q < 3; ++q) {
+            const int32_t k = gp_xnode[4 * j + q];
+            if (k < 0) continue;
+            const int64_t e = fill[k]++;
+            tr_pt[e] = gp_pt[j];
+            tr_gp[e] = (int32_t)j;
+            tr_w[e] = q == 0 ? 1.0 : gp_xu[2 * j + q - 1];
+            tr_slot[e] = 0xffffffffu;   // k_sg_asm does not walk these lists
+        }
     for (int64_t j = 0; j < ngp; ++j)
         for (int q0 = 0; q0 < 4; ++q0) {
             if (gp_wt[4 * j + q0] == 0.0) continue;
@@ -3109,9 +3249,11 @@ void sgrid_set(System& S, int64_t npts, const int32_t* h_grid, const int32_t* h_
     SgridData N;
     N.ng = ng; N.npts = npts; N.ntp = ntp; N.ngp = ngp; N.nent = nent;
     N.ntile = (int64_t)tile_grid.size(); N.nk = (int64_t)k_pos.size(); N.fsum = moff[ng];
-    for (int64_t g = 0; g < ng; ++g) N.ntot += nn[g];
+    for (int64_t g = 0; g < ng; ++g) N.ntot += nl[g];
     N.nbk = grid_for(ntp, BLOCK, BIAS_NPART);
-    N.h_nn = nn; N.h_npad = npad; N.h_poff = poff; N.h_moff = moff;
+    N.h_nn = nn; N.h_nl = nl; N.h_npad = npad; N.h_poff = poff; N.h_moff = moff;
+    N.nxt = nxt;
+    N.cl_id = cl_id; N.cl_id_node = cl_id_node; N.cl_grp = cl_grp; N.cl_grp_node = cl_grp_node;
     auto up = [&](auto& d, const auto& h) {
         d.alloc(std::max<int64_t>((int64_t)h.size(), 1));
         d.upload(h.data(), (int64_t)h.size(), S.stream);
@@ -3123,6 +3265,15 @@ void sgrid_set(System& S, int64_t npts, const int32_t* h_grid, const int32_t* h_
     up(N.gp_pt, gp_pt); up(N.gp_node, gp_node); up(N.gp_wt, gp_wt); up(N.nbr, nbr); up(N.node_grid, node_grid);
     up(N.poff, poff); up(N.moff, moff); up(N.npad, npad); up(N.nn, nn); up(N.tile_grid, tile_grid); up(N.tile_jb, tile_jb);
     up(N.k_pos, k_pos); up(N.k_val, k_sum);
+    up(N.nl, nl); up(N.nx, nx);
+    if (nxt) {
+        up(N.gp_xnode, gp_xnode); up(N.gp_xu, gp_xu);
+    }
+    N.nseg = nseg;
+    if (nseg) {
+        up(N.seg_ptr, seg_ptr); up(N.seg_lo, seg_lo); up(N.seg_hi, seg_hi);
+        N.seg_sum.alloc(nseg);
+    }
     N.w2.alloc(std::max<int64_t>(npts, 1));
     N.M.alloc(N.fsum); N.Ri.alloc(N.fsum);
     N.d0.alloc(ntp); N.err.alloc(ng);
@@ -3131,6 +3282,11 @@ void sgrid_set(System& S, int64_t npts, const int32_t* h_grid, const int32_t* h_
     HIP_CHECK(hipStreamSynchronize(S.stream));   // the uploads read host vectors of this scope
     N.on = npts > 0;
     graph_cache_drop(&S);   // captured iterations hold no elimination step yet
+    if (jb || js) {   // the grids' rows leave the bias / slope path
+        std::vector<uint8_t> sink(std::max<int64_t>(npts, 1), 0);
+        for (int64_t i = 0; i < npts; ++i) sink[i] = h_grid[i] >= 0;
+        bias_rebuild(S, sink.data());
+    }
     S.sgrid = std::move(N);
     S.cg_ready = false;
 }
@@ -3154,7 +3310,31 @@ void sgrid_values(System& S, const double* dbp) {
         HIP_CHECK(hipStreamSynchronize(S.stream));
         int64_t o = 0;
         for (int64_t s = 0; s < G.ng; ++s)
-            for (int64_t k = 0; k < G.h_nn[s]; ++k) G.aval[o++] = y[G.h_poff[s] + k];
+            for (int64_t k = 0; k < G.h_nl[s]; ++k) G.aval[o++] = y[G.h_poff[s] + k];
+        // the claimed biases and slopes are their blocks' dense nodes (bias_values ran before and left them 0)
+        // (the biases and slopes cannot change while grids are set: api.hip refuses their set and clear calls)
+        BiasData& B = S.bias;
+        if ((!G.cl_id.empty() && G.cl_id.back() >= B.nb) || (!G.cl_grp.empty() && G.cl_grp.back() >= B.ng))
+            throw std::logic_error("sensor grids: the claimed biases or slopes left the handle");
+        if (!G.cl_id.empty()) {
+            std::vector<double> b(B.nb);
+            B.bval.download(b.data(), B.nb, S.stream);
+            HIP_CHECK(hipStreamSynchronize(S.stream));
+            for (size_t t = 0; t < G.cl_id.size(); ++t) b[G.cl_id[t]] = y[G.cl_id_node[t]];
+            B.bval.upload(b.data(), B.nb, S.stream);
+            HIP_CHECK(hipStreamSynchronize(S.stream));
+        }
+        if (!G.cl_grp.empty()) {
+            std::vector<double> gv(2 * B.ng);
+            B.gval.download(gv.data(), 2 * B.ng, S.stream);
+            HIP_CHECK(hipStreamSynchronize(S.stream));
+            for (size_t t = 0; t < G.cl_grp.size(); ++t) {
+                gv[2 * G.cl_grp[t]] = y[G.cl_grp_node[t]];
+                gv[2 * G.cl_grp[t] + 1] = y[G.cl_grp_node[t] + 1];
+            }
+            B.gval.upload(gv.data(), 2 * B.ng, S.stream);
+            HIP_CHECK(hipStreamSynchronize(S.stream));
+        }
     }
     G.solved = true;
 }

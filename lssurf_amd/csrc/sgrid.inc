@@ -15,21 +15,51 @@
 // Reproducibility (SgridData, system.hpp): the transpose by node lists its entries in point order; a
 // wave sums them lane-strided and with the fixed shuffle tree; the triangular products add in index
 // order.  No atomics: two runs agree bit for bit.
+//
+// Beside data biases and slopes (lsq_set_sensor_grids_joint) a block also holds the bias IDs and slope
+// groups all of whose rows lie in its grid, as dense nodes behind the lattice nodes (SgridData): B gains
+// their columns, K their c² on the diagonal, k_sg_asmx forms their entries of M and k_sg_applyx applies
+// them; the other IDs and groups stay with bias.inc / slope.inc, and elim_* below runs both.
 
-// s_k = Σ_{e ∈ k} β_e src[pt_e]: a wave per padded node over its transpose entries
+// the segments of the long dense-node lists (SgridData::seg_*): a wave per segment, lane-strided, then
+// the fixed shuffle tree
+__global__ __launch_bounds__(BLOCK) void k_sg_btd_seg(const CgState* __restrict__ st, int64_t nseg,
+                                                      const int64_t* __restrict__ seg_lo,
+                                                      const int64_t* __restrict__ seg_hi,
+                                                      const int32_t* __restrict__ tr_pt,
+                                                      const double* __restrict__ tr_w, const double* __restrict__ src,
+                                                      double* __restrict__ seg_sum) {
+    if (st && st->stop) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t nw = (int64_t)gridDim.x * (BLOCK / 64);
+    for (int64_t j = (int64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6); j < nseg; j += nw) {   // wave-uniform
+        double t = 0.0;
+        for (int64_t e = seg_lo[j] + lane; e < seg_hi[j]; e += 64) t += tr_w[e] * src[tr_pt[e]];
+        t = wave_sum(t);
+        if (lane == 0) seg_sum[j] = t;
+    }
+}
+
+// s_k = Σ_{e ∈ k} β_e src[pt_e]: a wave per padded node over its transpose entries; seg_ptr (nullable):
+// a node with segments adds their sums (k_sg_btd_seg ran before) in segment order instead
 __global__ __launch_bounds__(BLOCK) void k_sg_btd(const CgState* __restrict__ st, int64_t ntp,
                                                   const int64_t* __restrict__ tr_ptr,
                                                   const int32_t* __restrict__ tr_pt,
                                                   const double* __restrict__ tr_w, const double* __restrict__ src,
-                                                  double* __restrict__ s) {
+                                                  double* __restrict__ s, const int32_t* __restrict__ seg_ptr,
+                                                  const double* __restrict__ seg_sum) {
     if (st && st->stop) return;
     const int lane = threadIdx.x & 63;
     const int64_t nw = (int64_t)gridDim.x * (BLOCK / 64);
     // whole waves leave the loop together: k is wave-uniform
     for (int64_t k = (int64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6); k < ntp; k += nw) {
         const int64_t lo = tr_ptr[k], hi = tr_ptr[k + 1];
+        const int32_t sa = seg_ptr ? seg_ptr[k] : 0, sb = seg_ptr ? seg_ptr[k + 1] : 0;
         double t = 0.0;
-        for (int64_t e = lo + lane; e < hi; e += 64) t += tr_w[e] * src[tr_pt[e]];
+        if (sb > sa)
+            for (int32_t j = sa + lane; j < sb; j += 64) t += seg_sum[j];
+        else
+            for (int64_t e = lo + lane; e < hi; e += 64) t += tr_w[e] * src[tr_pt[e]];
         t = wave_sum(t);
         if (lane == 0) s[k] = t;
     }
@@ -113,6 +143,91 @@ __global__ __launch_bounds__(BLOCK) void k_sg_apply(const CgState* __restrict__ 
         for (int64_t k = (int64_t)blockIdx.x * BLOCK + threadIdx.x; k < ntp; k += (int64_t)npart * BLOCK)
             acc -= s[k] * y[k];
         store_partial(acc, part, blockIdx.x);
+    }
+}
+
+// k_sg_apply for grids with dense nodes (lsq_set_sensor_grids_joint): a row carries up to three
+// further entries, its bias ID's node (coefficient 1) and its slope group's two nodes (u₀, u₁);
+// gp_xnode: −1 where the row has none (a row with a group has both of its nodes)
+__global__ __launch_bounds__(BLOCK) void k_sg_applyx(const CgState* __restrict__ st, int64_t ngp,
+                                                     const int32_t* __restrict__ gp_pt,
+                                                     const int4* __restrict__ gp_node,
+                                                     const double4* __restrict__ gp_wt,
+                                                     const int4* __restrict__ gp_xnode,
+                                                     const double2* __restrict__ gp_xu, const double* __restrict__ w2,
+                                                     const double* __restrict__ y, double* __restrict__ td, int mode,
+                                                     int64_t ntp, const double* __restrict__ s, double* part,
+                                                     int npart) {
+    if (st && st->stop) return;
+    for (int64_t j = (int64_t)blockIdx.x * BLOCK + threadIdx.x; j < ngp; j += (int64_t)gridDim.x * BLOCK) {
+        const int32_t i = gp_pt[j];
+        const int4 n = gp_node[j];
+        const double4 b = gp_wt[j];
+        const int4 xn = gp_xnode[j];
+        const double2 uu = gp_xu[j];
+        const double lat = ((b.x * y[n.x] + b.y * y[n.y]) + b.z * y[n.z]) + b.w * y[n.w];
+        const double yb = xn.x >= 0 ? y[xn.x] : 0.0;
+        const double ys = xn.y >= 0 ? uu.x * y[xn.y] + uu.y * y[xn.z] : 0.0;
+        const double d = w2[i] * (lat + (yb + ys));
+        td[i] = mode ? -d : td[i] - d;
+    }
+    if (part && (int)blockIdx.x < npart) {   // block-uniform
+        double acc = 0.0;
+        for (int64_t k = (int64_t)blockIdx.x * BLOCK + threadIdx.x; k < ntp; k += (int64_t)npart * BLOCK)
+            acc -= s[k] * y[k];
+        store_partial(acc, part, blockIdx.x);
+    }
+}
+
+// per solve, dense nodes set: row k of M in its block's dense columns.  A wave per padded node k
+// (lattice or dense) walks k's transpose entries; an entry's row adds w² β_k to the column of its ID
+// and w² β_k u₀, w² β_k u₁ to the columns of its group: one accumulator per dense slot of the block
+// (≤ SG_MAX_DENSE), chosen by compare, then the fixed shuffle tree.  A wave writes its own row only,
+// from the diagonal on (dense_spd_factor reads the upper triangle): every entry has one writer and
+// one order of summation.  Runs behind k_sg_asm, which left the identity on the dense nodes' rows.
+__global__ __launch_bounds__(BLOCK) void k_sg_asmx(int64_t ntp, const int64_t* __restrict__ tr_ptr,
+                                                   const int32_t* __restrict__ tr_pt,
+                                                   const int32_t* __restrict__ tr_gp,
+                                                   const double* __restrict__ tr_w,
+                                                   const int4* __restrict__ gp_xnode,
+                                                   const double2* __restrict__ gp_xu, const double* __restrict__ w2,
+                                                   const int32_t* __restrict__ node_grid,
+                                                   const int64_t* __restrict__ poff,
+                                                   const int64_t* __restrict__ moff,
+                                                   const int64_t* __restrict__ npad, const int64_t* __restrict__ nn,
+                                                   const int64_t* __restrict__ nl, const int64_t* __restrict__ nx,
+                                                   double* __restrict__ M) {
+    const int lane = threadIdx.x & 63;
+    const int64_t nw = (int64_t)gridDim.x * (BLOCK / 64);
+    for (int64_t k = (int64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6); k < ntp; k += nw) {   // wave-uniform
+        const int32_t g = node_grid[k];
+        const int64_t np = npad[g], p0 = poff[g], i = k - p0, nlg = nl[g];
+        const int nxg = (int)nx[g];
+        if (i >= nn[g] || nxg == 0) continue;   // padding, or a block without dense nodes
+        const int32_t d0 = (int32_t)(p0 + nlg);   // the block's first dense node
+        double acc[SG_MAX_DENSE];
+#pragma unroll
+        for (int c = 0; c < SG_MAX_DENSE; ++c) acc[c] = 0.0;
+        for (int64_t e = tr_ptr[k] + lane; e < tr_ptr[k + 1]; e += 64) {
+            const double ww = w2[tr_pt[e]] * tr_w[e];
+            const int4 xn = gp_xnode[tr_gp[e]];
+            const double2 uu = gp_xu[tr_gp[e]];
+            const int s0 = xn.x >= 0 ? xn.x - d0 : -1, s1 = xn.y >= 0 ? xn.y - d0 : -1, s2 = xn.z >= 0 ? xn.z - d0 : -1;
+            const double v1 = ww * uu.x, v2 = ww * uu.y;
+#pragma unroll
+            for (int c = 0; c < SG_MAX_DENSE; ++c) {
+                if (s0 == c) acc[c] += ww;
+                if (s1 == c) acc[c] += v1;
+                if (s2 == c) acc[c] += v2;
+            }
+        }
+        double mine = 0.0;
+#pragma unroll
+        for (int c = 0; c < SG_MAX_DENSE; ++c) {
+            const double t = wave_sum(acc[c]);
+            if (lane == c) mine = t;
+        }
+        if (lane < nxg && nlg + lane >= i) M[moff[g] + i * np + nlg + lane] = mine;
     }
 }
 
@@ -202,8 +317,11 @@ inline bool sgrid_active(const System& S) { return S.sgrid.on && !S.dist && cg_u
 // the three launches of y = M⁻¹ Bᵀ src
 void sgrid_launch_btd(const System& S, const CgState* st, const double* src) {
     const SgridData& G = S.sgrid;
+    if (G.nseg)
+        hipLaunchKernelGGL(k_sg_btd_seg, dim3(grid_for(G.nseg, BLOCK / 64)), dim3(BLOCK), 0, S.stream, st, G.nseg,
+                           G.seg_lo.p, G.seg_hi.p, G.tr_pt.p, G.tr_w.p, src, G.seg_sum.p);
     hipLaunchKernelGGL(k_sg_btd, dim3(grid_for(G.ntp, BLOCK / 64)), dim3(BLOCK), 0, S.stream, st, G.ntp, G.tr_ptr.p,
-                       G.tr_pt.p, G.tr_w.p, src, G.s.p);
+                       G.tr_pt.p, G.tr_w.p, src, G.s.p, G.nseg ? G.seg_ptr.p : (const int32_t*)nullptr, G.seg_sum.p);
 }
 
 void sgrid_launch_trsv_t(const System& S, const CgState* st) {
@@ -231,13 +349,21 @@ void sgrid_launch_reduce(const System& S, const CgState* st, const double* src, 
 
 // mode 0: td −= W² B y; mode 1: td = −W² B y (after sgrid_launch_reduce); part (nullable): G.nbk
 // partials of −Σ_k s_k y_k
-void sgrid_launch_apply(const System& S, const CgState* st, double* td, int mode, double* part) {
+// ngp (≤ G.ngp): 0 stores the partials alone.  Beside the biases (S.bias.on) their apply pass has
+// written every row in mode 1 already.
+void sgrid_launch_apply(const System& S, const CgState* st, double* td, int mode, double* part, int64_t ngp) {
     const SgridData& G = S.sgrid;
-    if (mode) HIP_CHECK(hipMemsetAsync(td, 0, sizeof(double) * (size_t)G.npts, S.stream));   // the rows outside every grid
-    const int grid = std::max(grid_for(G.ngp), G.nbk);
-    hipLaunchKernelGGL(k_sg_apply, dim3(grid), dim3(BLOCK), 0, S.stream, st, G.ngp, G.gp_pt.p,
-                       reinterpret_cast<const int4*>(G.gp_node.p), reinterpret_cast<const double4*>(G.gp_wt.p), G.w2.p,
-                       G.y.p, td, mode, G.ntp, G.s.p, part, G.nbk);
+    if (mode && !S.bias.on) HIP_CHECK(hipMemsetAsync(td, 0, sizeof(double) * (size_t)G.npts, S.stream));   // the rows outside every grid
+    const int grid = std::max(grid_for(ngp), G.nbk);
+    if (G.nxt)
+        hipLaunchKernelGGL(k_sg_applyx, dim3(grid), dim3(BLOCK), 0, S.stream, st, ngp, G.gp_pt.p,
+                           reinterpret_cast<const int4*>(G.gp_node.p), reinterpret_cast<const double4*>(G.gp_wt.p),
+                           reinterpret_cast<const int4*>(G.gp_xnode.p), reinterpret_cast<const double2*>(G.gp_xu.p),
+                           G.w2.p, G.y.p, td, mode, G.ntp, G.s.p, part, G.nbk);
+    else
+        hipLaunchKernelGGL(k_sg_apply, dim3(grid), dim3(BLOCK), 0, S.stream, st, ngp, G.gp_pt.p,
+                           reinterpret_cast<const int4*>(G.gp_node.p), reinterpret_cast<const double4*>(G.gp_wt.p), G.w2.p,
+                           G.y.p, td, mode, G.ntp, G.s.p, part, G.nbk);
 }
 
 // per solve (beside k_dmf_rs): w² per sorted point, M_s = Σ w² β βᵀ + K_s and its factor for the
@@ -250,7 +376,12 @@ void sgrid_prepare(System& S) {
     G.err.zero(st);
     hipLaunchKernelGGL(k_sg_asm, dim3(grid_for(G.ntp, BLOCK / 64)), dim3(BLOCK), 0, st, G.ntp, G.tr_ptr.p, G.tr_pt.p,
                        G.tr_gp.p, G.tr_slot.p, G.tr_w.p, G.gp_wt.p, G.w2.p, G.nbr.p, G.node_grid.p, G.poff.p, G.moff.p,
-                       G.npad.p, G.nn.p, G.M.p);
+                       G.npad.p, G.nl.p, G.M.p);   // the lattice nodes; the identity on the dense nodes and the padding
+    if (G.nxt)
+        hipLaunchKernelGGL(k_sg_asmx, dim3(grid_for(G.ntp, BLOCK / 64)), dim3(BLOCK), 0, st, G.ntp, G.tr_ptr.p,
+                           G.tr_pt.p, G.tr_gp.p, G.tr_w.p, reinterpret_cast<const int4*>(G.gp_xnode.p),
+                           reinterpret_cast<const double2*>(G.gp_xu.p), G.w2.p, G.node_grid.p, G.poff.p, G.moff.p,
+                           G.npad.p, G.nn.p, G.nl.p, G.nx.p, G.M.p);
     if (G.nk) hipLaunchKernelGGL(k_sg_addk, dim3(grid_for(G.nk)), dim3(BLOCK), 0, st, G.nk, G.k_pos.p, G.k_val.p, G.M.p);
     hipLaunchKernelGGL(k_sg_diag, dim3(grid_for(G.ntp)), dim3(BLOCK), 0, st, G.ntp, G.node_grid.p, G.poff.p, G.moff.p,
                        G.npad.p, G.M.p, G.d0.p, 0, G.err.p);
@@ -281,10 +412,11 @@ void sgrid_kernel_bytes(const System& S, double out[4]) {
         const double nb = (double)(G.h_npad[g] / 64);
         tri += nb * (nb + 1.0) / 2.0 * 64.0 * 64.0 * 8.0;
     }
-    out[0] = 20.0 * (double)G.nent + 16.0 * (double)G.ntp;
+    out[0] = 20.0 * (double)G.nent + 16.0 * (double)G.ntp + 32.0 * (double)G.nseg;   // a segment: its bounds, its sum written and read
     out[1] = tri + 16.0 * (double)G.ntp;
     out[2] = tri + 20.0 * (double)G.ntp;
     out[3] = 76.0 * (double)G.ngp + 24.0 * (double)G.ntp;
+    if (G.nxt) out[3] += 32.0 * (double)G.ngp;   // the dense entries: three nodes (an int4) and u (nent counts their transpose)
 }
 
 double sgrid_step_bytes(const System& S) {
@@ -293,25 +425,31 @@ double sgrid_step_bytes(const System& S) {
     return k[0] + k[1] + k[2] + k[3];
 }
 
-// ---- one interface over the two eliminations (biases / slopes, or sensor grids; never both) -----
-inline int elim_nbk(const System& S) { return bias_active(S) ? S.bias.nbk : (sgrid_active(S) ? S.sgrid.nbk : 0); }
+// ---- one interface over the two eliminations (biases / slopes, sensor grids, or both) ------------
+// Both (lsq_set_sensor_grids_joint): the rows of every grid belong to their block and the others to
+// the bias / slope path (its sink rank makes the grids' rows exact zeros there), so the two
+// corrections of td touch disjoint rows and add: both reduces read the same td, then both applies
+// run.  The partials lie one behind the other: the biases' S.bias.nbk, then the grids' S.sgrid.nbk.
+inline int elim_nbk(const System& S) { return (bias_active(S) ? S.bias.nbk : 0) + (sgrid_active(S) ? S.sgrid.nbk : 0); }
 inline const double* elim_w2(const System& S) { return S.sgrid.on ? S.sgrid.w2.p : S.bias.w2.p; }
 inline int64_t elim_npts(const System& S) { return S.sgrid.on ? S.sgrid.npts : S.bias.npts; }
+inline double* elim_sgrid_part(const System& S, double* part) { return part && S.bias.on ? part + S.bias.nbk : part; }
 
 // the eliminated unknowns for the sums of src; part (nullable) as in elim_launch_step.  With sensor
-// grids the partials are written by the apply pass: elim_launch_apply must follow with the same part.
+// grids their partials are written by the apply pass: elim_launch_apply must follow with the same part.
+// Both set: the marks E0 … E2 stand behind the grids' three launches, E0 spans the bias path's
+// reduce as well and E3 (elim_launch_step) both apply passes; with marks->bias_path they stand behind the bias path's three stages, and E3 behind
+// its apply pass, so that E3 spans the grids' reduce as well.
 void elim_launch_reduce(const System& S, const CgState* st, const double* src, double* part, CgMarks* marks = nullptr) {
-    if (S.sgrid.on)
-        sgrid_launch_reduce(S, st, src, marks);
-    else
-        bias_launch_reduce(S, st, src, part, marks);
+    const bool both = S.bias.on && S.sgrid.on, on_bias = marks && marks->bias_path;
+    if (S.bias.on) bias_launch_reduce(S, st, src, part, both && !on_bias ? nullptr : marks);
+    if (S.sgrid.on) sgrid_launch_reduce(S, st, src, both && on_bias ? nullptr : marks);
 }
 
-void elim_launch_apply(const System& S, const CgState* st, double* td, int mode, double* part) {
-    if (S.sgrid.on)
-        sgrid_launch_apply(S, st, td, mode, part);
-    else
-        bias_launch_apply(S, st, td, mode);
+void elim_launch_apply(const System& S, const CgState* st, double* td, int mode, double* part, CgMarks* marks = nullptr) {
+    if (S.bias.on) bias_launch_apply(S, st, td, mode);
+    if (S.bias.on && S.sgrid.on && marks && marks->bias_path) cg_mark(marks, CG_E3, S.stream);
+    if (S.sgrid.on) sgrid_launch_apply(S, st, td, mode, elim_sgrid_part(S, part), S.sgrid.ngp);
 }
 
 // the elimination step on td (W² A_d p per sorted point): td ← W (I − Q) W A_d p; part: elim_nbk
@@ -319,19 +457,15 @@ void elim_launch_apply(const System& S, const CgState* st, double* td, int mode,
 // and E3, the apply pass
 void elim_launch_step(const System& S, const CgState* st, double* td, double* part, CgMarks* marks = nullptr) {
     elim_launch_reduce(S, st, td, part, marks);
-    elim_launch_apply(S, st, td, 0, part);
-    cg_mark(marks, CG_E3, S.stream);
+    elim_launch_apply(S, st, td, 0, part, marks);
+    if (!(S.bias.on && S.sgrid.on && marks && marks->bias_path)) cg_mark(marks, CG_E3, S.stream);
 }
 
 // the partials alone (the norm of W b in the general start): src is left as it is
 void elim_launch_norm(const System& S, const CgState* st, const double* src, double* part) {
+    if (S.bias.on) bias_launch_reduce(S, st, src, part);
     if (S.sgrid.on) {
-        const SgridData& G = S.sgrid;
         sgrid_launch_reduce(S, st, src);
-        hipLaunchKernelGGL(k_sg_apply, dim3(G.nbk), dim3(BLOCK), 0, S.stream, st, (int64_t)0, G.gp_pt.p,
-                           reinterpret_cast<const int4*>(G.gp_node.p), reinterpret_cast<const double4*>(G.gp_wt.p),
-                           G.w2.p, G.y.p, (double*)nullptr, 0, G.ntp, G.s.p, part, G.nbk);
-    } else {
-        bias_launch_reduce(S, st, src, part);
+        sgrid_launch_apply(S, st, nullptr, 0, elim_sgrid_part(S, part), 0);
     }
 }

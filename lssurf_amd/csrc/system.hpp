@@ -361,6 +361,12 @@ struct BiasData {
     DBuf<double> tmp;               // sorted point -> w² u_k (per solve)
     DBuf<double> gval;              // group -> slopes of the last solve
     std::vector<int32_t> h_grp;     // the caller's groups (empty: none)
+    std::vector<double> h_u, h_gc;  // and their coefficients and c: the joint sensor grids rebuild the layout
+    // Sensor grids set beside the biases (lsq_set_sensor_grids_joint): the rows of every grid belong to
+    // their grid's block.  Here they form one last rank (the sink) with c² = +∞: its D is +∞, so its
+    // s / D and its share of the partial are exactly 0, and the apply pass leaves its rows as they are.
+    bool sink = false;
+    std::vector<uint8_t> h_sink;    // row -> lies in a grid (empty: no sink)
 };
 
 // Sensor bias grids eliminated from the CGNR normal equations (lsq_set_sensor_grids; sgrid.inc): the
@@ -373,6 +379,8 @@ struct BiasData {
 constexpr int64_t SG_MAX_NODES = 2048;                      // LSQ_SGRID_MAX_NODES
 constexpr int64_t SG_MAX_FACTOR_BYTES = (int64_t)1 << 30;   // LSQ_SGRID_MAX_FACTOR_BYTES
 constexpr int SG_NBR = 9;                                   // distinct nodes that share a row with one node
+constexpr int64_t SG_SEG = 2048;                            // entries per segment of a long dense-node list (32 per lane)
+constexpr int SG_MAX_DENSE = 16;                           // LSQ_SGRID_MAX_DENSE
 struct SgridData {
     bool on = false;
     bool solved = false;            // aval belongs to the last lsq_solve's x
@@ -403,6 +411,26 @@ struct SgridData {
     DBuf<int> err;                  // per grid: a pivot that is not positive
     DBuf<double> s, z, y;           // padded node: Bᵀ src, R⁻ᵀ s, M⁻¹ s of the last reduction
     std::vector<double> aval;       // node -> grid value of the last solve
+    // Set beside data biases and slopes (lsq_set_sensor_grids_joint): a bias ID or a slope group whose
+    // rows all lie in grid s is a "dense node" of block s, behind its lattice nodes (local nodes
+    // nl_s … nl_s + nx_s − 1, nx_s ≤ SG_MAX_DENSE, a group takes two).  A dense node's transpose list
+    // holds every row of its ID (weight 1) or group (weight u), and a grid point carries up to three
+    // dense entries (its ID, its group's x and y) beside the four lattice ones.  nn counts both kinds;
+    // the lattice nodes alone are nl.  The rows of every grid leave the bias / slope path (a sink rank
+    // with D = +∞, BiasData::sink).
+    int64_t nxt = 0;                // dense nodes of all grids (0: the four-entry kernels, as without biases)
+    std::vector<int64_t> h_nl;      // per grid: lattice nodes
+    DBuf<int64_t> nl, nx;           // per grid: lattice nodes, dense nodes
+    DBuf<int32_t> gp_xnode;         // 4 per grid point: the padded nodes of its ID, group x, group y (−1: none), unused
+    DBuf<double> gp_xu;             // 2 per grid point: u of its group's row (0 without a group)
+    // A dense node's list is as long as its sensor; over SG_SEG entries it is cut into segments of SG_SEG,
+    // a wave each (k_sg_btd_seg), and the node's wave adds the segments' sums in segment order.
+    int64_t nseg = 0;
+    DBuf<int32_t> seg_ptr;          // padded node -> first segment (ntp + 1); no segments: the node's wave walks its list
+    DBuf<int64_t> seg_lo, seg_hi;   // segment -> its transpose entries [lo, hi)
+    DBuf<double> seg_sum;           // segment -> its sum of the last reduction
+    std::vector<int32_t> cl_id, cl_id_node;    // claimed bias IDs and their padded nodes
+    std::vector<int32_t> cl_grp, cl_grp_node;   // claimed slope groups and the padded node of their x slope (y: the next)
 };
 
 // Extra sparse rows behind the stencil rows (lsq_set_extra_rows; xrows.inc): ≤ XR_MAXW entries per

@@ -152,3 +152,37 @@ def sensor_grid_device_form(data, grids, sensor_of, constraint_ops):
         shift.append(ev)
     return dict(grid=gid, node=node, wt=wt, n_nodes=np.array(n_nodes, dtype=np.int64), K=K,
                 shift=np.array(shift, dtype=float), names=list(sensor_of))
+
+
+def joint_split(grid, ids=None, n_ids=0, grp=None, n_groups=0):
+    """How the joint elimination (lsq_set_sensor_grids_joint) sorts the biases and slopes of a fit by
+    owner.  grid: the grid of every data row (−1: none); ids: the rows' bias IDs in [0, n_ids); grp: the
+    rows' slope groups (−1: none) in [0, n_groups).  An ID or group with a row in a grid must have all
+    its rows (grp ≥ 0) in that grid, whose block claims it; the others stay on the bias / slope path.
+    -> dict(id_grid (n_ids,), grp_grid (n_groups,): the claiming grid or −1; dense: per grid the list
+    of its dense nodes, ('id', j) in ID order and then ('slope_x', s), ('slope_y', s) in group order,
+    which follow the grid's lattice nodes).  ValueError when the layout is not nested."""
+    grid = np.ravel(grid)
+    ng = int(grid.max()) + 1 if grid.size else 0
+
+    def owners(label, n, what):
+        out = np.full(n, -1, dtype=np.int64)
+        on = label >= 0
+        lo = np.full(n, np.iinfo(np.int64).max)
+        hi = np.full(n, -2, dtype=np.int64)
+        np.minimum.at(lo, label[on], grid[on])
+        np.maximum.at(hi, label[on], grid[on])
+        seen = hi > -2
+        if np.any(lo[seen] != hi[seen]):
+            bad = int(np.flatnonzero(seen & (lo != hi))[0])
+            raise ValueError(f'joint_split: the layout is not nested ({what} {bad} has rows in a grid and outside it, '
+                             f'or in two grids)')
+        out[seen] = hi[seen]
+        return out
+
+    id_grid = owners(np.ravel(ids).astype(np.int64), int(n_ids), 'bias ID') if ids is not None else np.zeros(0, np.int64)
+    grp_grid = owners(np.ravel(grp).astype(np.int64), int(n_groups), 'slope group') if grp is not None \
+        else np.zeros(0, np.int64)
+    dense = [[('id', int(j)) for j in np.flatnonzero(id_grid == s)] +
+             [(k, int(q)) for q in np.flatnonzero(grp_grid == s) for k in ('slope_x', 'slope_y')] for s in range(ng)]
+    return dict(id_grid=id_grid, grp_grid=grp_grid, dense=dense)

@@ -22,7 +22,9 @@ lsq_prior_mg=True lets the multigrid preconditioner (precond 4) carry them, lump
 Slope biases (data_slope_sensors) go with the data biases: they need bias_params and lsq_bias.
 Sensor bias grids (sensor_grid_bias_params; setup_sensor_grid_bias.py) run under the same key lsq_bias:
 'eliminate' (one dense block per grid eliminated inside CGNR, lsq_set_sensor_grids; not together with
-bias_params, data_slope_sensors or priors), 'columns' or 'auto'.
+bias_params, data_slope_sensors or priors), 'columns' or 'auto'.  lsq_sgrid_joint=True lets 'eliminate'
+and 'auto' run the grids beside bias_params and data_slope_sensors (lsq_set_sensor_grids_joint: every
+bias ID and slope group inside one grid's sensor or outside every grid); priors stay refused.
 Data biases (bias_params) run when the solver key lsq_bias says how: 'eliminate' (the device
 eliminates them inside CGNR, lsq_set_data_bias), 'columns' (ordinary columns of a generic system)
 or 'auto' (with priors: 'columns', with a warning where it would have eliminated).
@@ -75,7 +77,10 @@ DEFAULTS = {'reference_epoch': 0, 'W_ctr': 1e4, 'return_fit_objects': False, 'ma
             'lsq_bias': None,
             # priors (prior_args / prior_edge_args) inside the multigrid preconditioner: their rows
             # lumped into its coarse levels (opt-in; without priors the key does nothing)
-            'lsq_prior_mg': False, 'lsq_E_border': False}
+            'lsq_prior_mg': False, 'lsq_E_border': False,
+            # sensor bias grids beside bias_params / data_slope_sensors eliminated jointly (opt-in; the
+            # bias IDs and slope groups must nest in the grids' sensors, as with 'sensor' in bias_params)
+            'lsq_sgrid_joint': False}
 
 OUT_OF_SCOPE = ('lagrangian_coords', 'constraint_scaling_maps', 'mask_file', 'bias_edit_vals')
 
@@ -85,9 +90,12 @@ class FitSystem:
     Ip_c as a column map; rows re-weighted / re-selected per outer iteration."""
 
     def __init__(self, G_data, Gc, keep_cols, n_full, device=0, structured=True, grids=None, bias=None,
-                 extra_ops=None, extra_csr=None, extra_mg=False, sensor_grids=None):
+                 extra_ops=None, extra_csr=None, extra_mg=False, sensor_grids=None, joint=False):
         """sensor_grids: the dict of setup_sensor_grid_bias.sensor_grid_device_form — eliminated sensor
-        bias grids (LSQSolver.set_sensor_grids), not together with bias.  G_data and Gc are the
+        bias grids (LSQSolver.set_sensor_grids), together with bias only when joint=True
+        (lsq_set_sensor_grids_joint: every bias ID and slope group inside one grid's rows or outside
+        every grid; expand() then lays the columns out as the reference does: the biases, the slopes,
+        the sensor grids).  G_data and Gc are the
         operators without the grids' columns and constraint rows, the caller's row weights and rhs may
         carry the grids' constraint rows behind them, and the grids take the columns after n_full in
         expand().  A grid's uniform magnitude prior (shift) never reaches the device: the rhs of the
@@ -215,7 +223,7 @@ class FitSystem:
                 raise
         self.sg, self.sg_vals = None, None
         if sensor_grids is not None:
-            if bias is not None:
+            if bias is not None and not joint:
                 self.solver.close()
                 raise ValueError('FitSystem: sensor_grids and bias do not go together')
             # matrix-free CGNR only, never the dense preconditioner (LSQR).  Unlike the biases the grids leave
@@ -224,7 +232,7 @@ class FitSystem:
             try:
                 sg = dict(sensor_grids)
                 sg['grid'] = np.asarray(sg['grid']).astype(np.int32)
-                self.solver.set_sensor_grids(sg['grid'], sg['node'], sg['wt'], sg['n_nodes'], sg['K'])
+                self.solver.set_sensor_grids(sg['grid'], sg['node'], sg['wt'], sg['n_nodes'], sg['K'], joint=bool(joint))
             except Exception:
                 self.solver.close()
                 raise
@@ -293,11 +301,14 @@ class FitSystem:
     def expand(self, x):
         if self.bias_ids is not None:   # the biases of the last solve, in the columns after the grids
             n_slope = 0 if self.slope_grp is None else self.slope_vals.size
-            m0 = np.zeros(self.n_full + self.bias_vals.size + n_slope)
+            n_sg = 0 if self.sg is None else self.sg_vals.size
+            m0 = np.zeros(self.n_full + self.bias_vals.size + n_slope + n_sg)
             m0[self.n_full:self.n_full + self.bias_vals.size] = self.bias_vals
             if n_slope:   # behind the biases, (x, y) per group
-                m0[self.n_full + self.bias_vals.size:] = self.slope_vals.ravel()
-        elif self.sg is not None:       # the grids of the last solve, in the columns after the others
+                m0[self.n_full + self.bias_vals.size:m0.size - n_sg] = self.slope_vals.ravel()
+            if n_sg:      # joint: the sensor grids behind the slopes
+                m0[m0.size - n_sg:] = self.sg_vals
+        elif self.sg is not None:      # the grids of the last solve, in the columns after the others
             m0 = np.zeros(self.n_full + self.sg_vals.size)
             m0[self.n_full:] = self.sg_vals
         else:
@@ -688,7 +699,7 @@ def parse_model(m, m0, data, R, RMS, G_data, averaging_ops, Gc, Ec, grids, args,
 
 
 def _bias_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, bias_model, mode, grids, device, args,
-                     prior_ops=()):
+                     prior_ops=(), sgrid=None):
     """The device system of a fit with data biases.  'eliminate': the grid-only operators on the
     device plus lsq_set_data_bias (the bias constraint rows are the last rows of Gc, so the device
     rows are a prefix of the host rows); 'columns': the biases as ordinary columns of a generic
@@ -700,10 +711,13 @@ def _bias_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, bias_model, m
     With prior_ops (the priors behind the bias constraint rows of Gc) only 'columns' runs: the device
     rows of 'eliminate' are a prefix of the host rows, which rows behind the bias constraints would
     break.  smooth_fit refuses 'eliminate' with priors; 'auto' takes 'columns' and warns where it
-    would have eliminated, since the generic system costs the memory and speed of matrix-free CGNR."""
+    would have eliminated, since the generic system costs the memory and speed of matrix-free CGNR.
+    sgrid = (sensor_of, constraint_op_list) (lsq_sgrid_joint): sensor bias grids whose columns follow the
+    slopes' in G_data, eliminated jointly with the biases (lsq_set_sensor_grids_joint).  Where the device
+    refuses (an ID or group that does not nest in the grids, a cap) 'eliminate' raises and 'auto' warns
+    and takes 'columns'."""
     n_grid = G_grid.col_N if G_grid is not None else None
     slope_dict = bias_model.get('slope_bias_dict', {})
-    n_bias = int(G_data.col_N) - int(n_grid) - 2 * len(slope_dict) if n_grid is not None else 0
     if mode == 'auto' and (describe(G_grid, Gc_grid, with_fields=True) is None or
                            np.count_nonzero(keep_cols < n_grid) <= args['lsq_dense_max'] or
                            args['lsq_method'] == 'lsqr' or args['lsq_precond'] == 2):
@@ -714,6 +728,9 @@ def _bias_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, bias_model, m
                       RuntimeWarning, stacklevel=3)
         mode = 'columns'
     if mode != 'columns':
+        sg = sensor_grid_device_form(data, grids, *sgrid) if sgrid is not None else None
+        n_sg = int(np.sum(sg['n_nodes'])) if sg is not None else 0
+        n_bias = int(G_data.col_N) - int(n_grid) - 2 * len(slope_dict) - n_sg
         ids = np.asarray(data.bias_ID).astype(np.int32)
         c = 1. / bias_expected(bias_model, n_bias)
         bias = (ids, c)
@@ -722,10 +739,13 @@ def _bias_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, bias_model, m
             bias += ((group, u, np.full((len(slope_dict), 2), 1. / (bias_model['E_slope_bias'] * SLOPE_RESCALE))),)
         try:
             return FitSystem(G_grid, Gc_grid, keep_cols[keep_cols < n_grid], n_grid, device=device, grids=grids,
-                             bias=bias)
-        except NativeError:
+                             bias=bias, sensor_grids=sg, joint=sg is not None)
+        except NativeError as e:
             if mode == 'eliminate':
                 raise
+            if sg is not None:
+                warnings.warn(f"smooth_fit: lsq_bias='auto' with lsq_sgrid_joint takes 'columns': the device refuses "
+                              f"the joint elimination ({e})", RuntimeWarning, stacklevel=3)
     return FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=device, grids=grids)
 
 
@@ -778,6 +798,8 @@ def smooth_fit(**kwargs):
         raise ValueError(f"smooth_fit: lsq_prior_mg must be True or False, not {args['lsq_prior_mg']!r}")
     if not isinstance(args['lsq_E_border'], (bool, np.bool_)):
         raise ValueError(f"smooth_fit: lsq_E_border must be True or False, not {args['lsq_E_border']!r}")
+    if not isinstance(args['lsq_sgrid_joint'], (bool, np.bool_)):
+        raise ValueError(f"smooth_fit: lsq_sgrid_joint must be True or False, not {args['lsq_sgrid_joint']!r}")
     bias_mode = args['lsq_bias']
     if args['bias_params'] is not None:
         if bias_mode is None:
@@ -801,7 +823,7 @@ def smooth_fit(**kwargs):
 
     has_priors = args.get('prior_args') is not None or args.get('prior_edge_args') is not None
     has_sgrids = args.get('sensor_grid_bias_params') is not None and len(args['sensor_grid_bias_params']) > 0
-    sgrid_mode = None
+    sgrid_mode, sgrid_joint = None, False
     if has_sgrids:
         # sensor bias grids: the same key says how they run, and the refusals of bias_params hold
         sgrid_mode = bias_mode
@@ -821,7 +843,10 @@ def smooth_fit(**kwargs):
         if sgrid_mode == 'eliminate' and args['lsq_precond'] not in ('auto', 1, 3, 4):
             raise NotImplementedError("smooth_fit: lsq_bias='eliminate' runs CGNR with lsq_precond 'auto', 1, 3 or "
                                       "4; the dense preconditioner needs lsq_bias='columns'")
-        if args['bias_params'] is not None or has_slopes or has_priors:
+        # lsq_sgrid_joint: the biases and slopes that nest in the grids' sensors join their grid's block
+        sgrid_joint = bool(args['lsq_sgrid_joint']) and args['bias_params'] is not None and not has_priors and \
+            sgrid_mode != 'columns'
+        if (args['bias_params'] is not None or has_slopes or has_priors) and not sgrid_joint:
             # the joint eliminated block is no longer one dense block per grid
             if sgrid_mode == 'eliminate':
                 raise NotImplementedError("smooth_fit: sensor_grid_bias_params with lsq_bias='eliminate' does not go "
@@ -920,7 +945,7 @@ def smooth_fit(**kwargs):
     # without them, which the device holds when it eliminates the grids itself
     sgrid_sensor = {}
     if has_sgrids:
-        if sgrid_mode != 'columns':
+        if sgrid_mode != 'columns' and not sgrid_joint:   # joint: the operators without the biases, made above
             G_grid = interp_ops()
             Gc_grid = lin_op(None, name='constraints').vstack(list(constraint_op_list))
         for params in args['sensor_grid_bias_params']:
@@ -933,7 +958,7 @@ def smooth_fit(**kwargs):
                     op.prior = np.zeros(np.shape(op.expected))
                     zero_prior.add(op.name)
         if not sgrid_sensor:
-            has_sgrids, sgrid_mode = False, None
+            has_sgrids, sgrid_mode, sgrid_joint = False, None, False
     sgrid_ops = {'grad2_' + name for name in sgrid_sensor} | {'mag_' + name for name in sgrid_sensor}
     # priors, in the reference's order (smooth_fit.py:575-582), behind every other constraint
     prior_ops = []
@@ -1009,7 +1034,8 @@ def smooth_fit(**kwargs):
                 system = MultiDeviceFitSystem(G_data, Gc, keep_cols, Gc.col_N, devices)
             elif bias_model:
                 system = _bias_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, bias_model,
-                                          bias_mode, grids, devices[0], args, prior_ops=prior_ops)
+                                          bias_mode, grids, devices[0], args, prior_ops=prior_ops,
+                                          sgrid=(sgrid_sensor, constraint_op_list) if sgrid_joint else None)
             elif has_sgrids and not prior_ops:
                 system = _sgrid_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, sgrid_sensor,
                                            constraint_op_list, sgrid_mode, grids, devices[0], args)
@@ -1023,6 +1049,8 @@ def smooth_fit(**kwargs):
             system.b_rows = b_rows
             if has_sgrids:   # how the sensor bias grids ran
                 timing['sensor_grids'] = 'eliminate' if getattr(system, 'sg', None) is not None else 'columns'
+                timing['sgrid_joint'] = timing['sensor_grids'] == 'eliminate' and \
+                    getattr(system, 'bias_ids', None) is not None
             timing['formation'] = getattr(system, 'formation', None)   # 'stencil' or 'coo'
             timing['extra_rows'] = int(getattr(system, 'n_extra', 0))  # prior rows the device holds as extra rows
             timing['device_setup'] = time() - tic

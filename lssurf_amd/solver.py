@@ -340,9 +340,11 @@ class LSQSolver:
         self._check(self._L.lsq_profile_data_slope(self._h, int(reps), int(precond), ptr(o)), 'lsq_profile_data_slope')
         return {k: (float(o[i]), float(o[4 + i])) for i, k in enumerate(('chunk', 'rank', 'group', 'apply'))}
 
-    def set_sensor_grids(self, grid, node, wt, n_nodes, K):
+    def set_sensor_grids(self, grid, node, wt, n_nodes, K, joint=False):
         """A coarse grid of additive bias per sensor on the data rows, each eliminated as one dense
-        block inside CGNR (lsq_set_sensor_grids); not together with set_data_bias / set_data_slope.
+        block inside CGNR (lsq_set_sensor_grids); not together with set_data_bias / set_data_slope
+        unless joint=True (lsq_set_sensor_grids_joint; call it after them): every bias ID and slope
+        group must then lie inside one grid's rows, whose block takes it in, or outside every grid.
 
         grid: the grid of every data row (caller's row order), −1 for none, else in [0, len(n_nodes));
         node, wt: (rows, 4) nodes local to the row's grid and their weights (weight 0 pads a dropped
@@ -364,9 +366,9 @@ class LSQSolver:
         k_row = as_c(np.concatenate([np.ravel(k[0]) for k in K]) if k_ptr[-1] else np.zeros(1), np.int32)
         k_col = as_c(np.concatenate([np.ravel(k[1]) for k in K]) if k_ptr[-1] else np.zeros(1), np.int32)
         k_val = as_c(np.concatenate([np.ravel(k[2]) for k in K]) if k_ptr[-1] else np.zeros(1), np.float64)
-        self._check(self._L.lsq_set_sensor_grids(self._h, grid.size, ptr(grid), ptr(node), ptr(wt), n_nodes.size,
-                                                 ptr(n_nodes), ptr(k_ptr), ptr(k_row), ptr(k_col), ptr(k_val)),
-                    'lsq_set_sensor_grids')
+        name = 'lsq_set_sensor_grids_joint' if joint else 'lsq_set_sensor_grids'
+        self._check(getattr(self._L, name)(self._h, grid.size, ptr(grid), ptr(node), ptr(wt), n_nodes.size,
+                                           ptr(n_nodes), ptr(k_ptr), ptr(k_row), ptr(k_col), ptr(k_val)), name)
         self._sg_nodes = int(n_nodes.sum())
 
     def sensor_grids(self):
