@@ -90,7 +90,7 @@ class FitSystem:
     Ip_c as a column map; rows re-weighted / re-selected per outer iteration."""
 
     def __init__(self, G_data, Gc, keep_cols, n_full, device=0, structured=True, grids=None, bias=None,
-                 extra_ops=None, extra_csr=None, extra_mg=False, sensor_grids=None, joint=False):
+                 extra_ops=None, extra_csr=None, extra_mg=False, sensor_grids=None, joint=False, iterative=True):
         """sensor_grids: the dict of setup_sensor_grid_bias.sensor_grid_device_form — eliminated sensor
         bias grids (LSQSolver.set_sensor_grids), together with bias only when joint=True
         (lsq_set_sensor_grids_joint: every bias ID and slope group inside one grid's rows or outside
@@ -117,7 +117,12 @@ class FitSystem:
         extra_mg: ask the device to lump the extra rows into the multigrid's coarse levels
         (LSQSolver.set_extra_rows(lump=True)), so that precond 4 may carry them; where the device
         refuses (e.g. a row over non-adjacent epochs) multigrid_available warns with its reason and
-        the system stays on block-Jacobi."""
+        the system stays on block-Jacobi.
+        iterative: False when every solve will be LSQR with precond 2 or 5; extra rows that CGNR cannot
+        carry then stay on the stencil-formed system instead of taking the COO path.  With
+        iterative=True a system with extra rows, and any system with bias or sensor_grids, asks
+        cg_available(1) here: the column norms and the CGNR operator's description are built at
+        construction (smooth_fit's timing['device_setup']) and not at the first solve."""
         self.n_data, self.n_con = int(G_data.N_eq), int(Gc.N_eq)
         self.keep_cols = keep_cols
         self.n_full = int(n_full)
@@ -141,8 +146,13 @@ class FitSystem:
         if desc is not None:       # rows generated on the device from the grids and stencils
             gdesc, interp, coords, stencils, npts, fields = desc
             # Only a refusal of the extra rows themselves leads to the COO path, and it says so: at staging
-            # (e.g. > 32 entries in one row), or at formation when the other rows did not come out
-            # matrix-free ('extra rows need …').  Any other formation error stays an error.
+            # (e.g. > 32 entries in one row), at formation when the other rows did not come out
+            # matrix-free ('extra rows need …'), or behind it when the formed system has no CGNR operator
+            # that carries them (16 and more epochs: tile mode, or none at all).  There method 1, and LSQR
+            # on the structured operator with precond 1 or 3, raise at every solve; only LSQR with the
+            # dense or band preconditioner (2, 5) runs on the stencil-formed system, so a caller that
+            # solves that way alone passes iterative=False and keeps it.  Any other formation error stays
+            # an error.
             try:
                 if n_extra:        # staged first: they become the last rows of the formation
                     self.solver.set_extra_rows(*(extra_csr if extra_csr is not None else _extra_rows_csr(extra_ops)),
@@ -161,9 +171,13 @@ class FitSystem:
                     if not n_extra or extra_csr is not None or 'extra rows need' not in str(e):
                         raise
                     refusal = e
+            if refusal is None and n_extra and iterative:
+                ok, why = self.solver.cg_available(1)
+                if not ok:
+                    refusal, self.n_extra = why, 0
             if refusal is not None:
                 warnings.warn(f'FitSystem: the device refuses the {n_extra} extra rows ({refusal}); the whole '
-                              f'system is formed from triplets (COO) and loses matrix-free CGNR',
+                              f'system is formed from triplets (COO) and has no matrix-free CGNR',
                               RuntimeWarning, stacklevel=2)
                 self.solver.close()   # a fresh handle: nothing staged, nothing half formed
                 self.solver = LSQSolver(device)
@@ -174,8 +188,13 @@ class FitSystem:
         if desc is None:           # generic lin_op: host triplets -> device CSR
             r1, c1, v1 = G_data.triplets()
             r2, c2, v2 = Gc.triplets()
-            self.solver.set_matrix_coo(m, self.n_full, np.concatenate([r1, r2 + self.n_data]),
-                                       np.concatenate([c1, c2]), np.concatenate([v1, v2]))
+            rr, cc, vv = [r1, r2 + self.n_data], [c1, c2], [v1, v2]
+            if extra_csr is not None:   # refused above: the rows behind Gc's as triplets
+                ip = np.asarray(extra_csr[0], np.int64)
+                rr.append(self.n_data + int(Gc.N_eq) + np.repeat(np.arange(ip.size - 1), np.diff(ip)))
+                cc.append(np.asarray(extra_csr[1], np.int64))
+                vv.append(np.asarray(extra_csr[2], float))
+            self.solver.set_matrix_coo(m, self.n_full, np.concatenate(rr), np.concatenate(cc), np.concatenate(vv))
         self.has_blocks = False
         self._grids, self._blocks = grids, None
         if grids is not None:      # per-node column blocks for the block-Jacobi preconditioner
@@ -244,6 +263,15 @@ class FitSystem:
             self.sg_cols = self.sg_off[sg['grid'][on]][:, None] + np.asarray(sg['node'])[on]
             self.sg_wt = np.asarray(sg['wt'], dtype=float)[on]
             self.sg_row_shift = np.asarray(sg['shift'], dtype=float)[sg['grid'][on]]
+        if bias is not None or sensor_grids is not None:
+            # The device takes the biases wherever the data rows came out matrix-free, but only the
+            # column-mode CGNR step eliminates them: with 16 epochs (dim 2 ≤ CG_MAXT, yet the dz stencil's
+            # strip no longer fits the ring) the set calls succeed and every solve would raise.  Ask now,
+            # so that 'eliminate' fails here and 'auto' takes 'columns' (found by tests/test_gpu_cgnr_tile.py)
+            ok, why = self.solver.cg_available(1)
+            if not ok:
+                self.solver.close()
+                raise NativeError(f'FitSystem: the elimination cannot run on this system: {why}')
 
     @property
     def blocks(self):
@@ -1040,8 +1068,12 @@ def smooth_fit(**kwargs):
                 system = _sgrid_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, sgrid_sensor,
                                            constraint_op_list, sgrid_mode, grids, devices[0], args)
             else:
+                # the dense (2) or band (5) preconditioner: LSQR on the stencil-formed system carries extra rows
+                dense = args['lsq_precond'] in (2, 5) or (args['lsq_precond'] == 'auto' and
+                                                          keep_cols.size <= args['lsq_dense_max'])
                 system = FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=devices[0], grids=grids,
-                                   extra_ops=prior_ops, extra_mg=bool(args['lsq_prior_mg']) and bool(prior_ops))
+                                   extra_ops=prior_ops, extra_mg=bool(args['lsq_prior_mg']) and bool(prior_ops),
+                                   iterative=not dense)
             if b_rows_all is not None and not getattr(system, 'n_extra', 0):
                 b_rows = max(b_rows, b_rows_all)
             if b_rows_sg is not None and getattr(system, 'sg', None) is None:

@@ -148,6 +148,14 @@ KS9 = tuple(k for k in KS if k <= 9)
 KSWEEP = [((9, 11), 300), ((7, 70), 600)]  # (ny, nx) nodes, points
 KSWEEP_NT = (2, 3, 5, 8, 13)
 MASK_SEED, X0_SEED, KSWEEP_SEED = 11, 13, 20260101
+# tests/test_gpu_cgnr_tile.py: 16 and more epochs, where the CGNR operator leaves column mode.  (7, 70):
+# two x tiles, rows no multiple of the tile's; (5, 200): x tiles clear of both edges; (9, 11): small
+# enough for the dense oracle (15: the last column-mode size, 20: no CGNR operator at all)
+TILE_SWEEP = [((7, 70), 600), ((5, 200), 900)]
+TILE_NT = (16, 17, 19)
+TILE_DENSE = ((9, 11), 300)
+TILE_DENSE_NT = (16, 19, 20)
+TILE_MASKED = [((5, 200), 19), ((7, 70), 16)]
 
 
 class Host:
@@ -201,11 +209,9 @@ def golden_host(name='sf3d'):
     return Host(LS.smooth_fit(data=golden_points(g), return_fit_objects=True, **kw), kw['reference_epoch'])
 
 
-@functools.lru_cache(maxsize=None)
-def ksweep_host(shape, npts, nt):
-    """A (ny, nx) lattice with nt epochs (node blocks of nt columns) and npts points, built as
-    lssurf_amd.synthetic does (config_kwargs / points) with a seed of its own."""
-    import lssurf_amd as LS
+def ksweep_points(shape, npts, nt):
+    """(data, smooth_fit keywords) of a (ny, nx) lattice with nt epochs (node blocks of nt columns) and
+    npts points, built as lssurf_amd.synthetic does (config_kwargs / points) with a seed of its own."""
     from lssurf_amd import containers as pc
     from lssurf_amd.synthetic import E_RMS_NOTEBOOK
     ny, nx = shape
@@ -216,7 +222,14 @@ def ksweep_host(shape, npts, nt):
     x, y, t = ((rng.random(npts) - 0.5) * W[d] for d in ('x', 'y', 't'))
     z = 10 * np.sin(4 * np.pi * x / max(W['x'], 1.)) * np.cos(6 * np.pi * y / max(W['y'], 1.)) + 0.5 * t \
         + rng.normal(0, 0.1, npts)
-    D = pc.data().from_dict({'x': x, 'y': y, 'time': t, 'z': z, 'sigma': np.full(npts, 0.1)})
+    return pc.data().from_dict({'x': x, 'y': y, 'time': t, 'z': z, 'sigma': np.full(npts, 0.1)}), kw
+
+
+@functools.lru_cache(maxsize=None)
+def ksweep_host(shape, npts, nt):
+    """The system of ksweep_points on the host."""
+    import lssurf_amd as LS
+    D, kw = ksweep_points(shape, npts, nt)
     return Host(LS.smooth_fit(data=D, return_fit_objects=True, VERBOSE=False, **kw), kw['reference_epoch'])
 
 
@@ -268,22 +281,25 @@ def rel(a, b):
 
 
 BLOCK_CASES = ['t64', 't64-mask', 'sf3d', 't15', 't64z', 'priors'] + \
-    [f'ksweep-{ny}x{nx}-{nt}' for (ny, nx), _ in KSWEEP for nt in KSWEEP_NT]
+    [f'ksweep-{ny}x{nx}-{nt}' for (ny, nx), _ in KSWEEP for nt in KSWEEP_NT] + \
+    [f'tile-{ny}x{nx}-{nt}' for (ny, nx), _ in TILE_SWEEP for nt in TILE_NT] + \
+    [f'tile-{TILE_DENSE[0][0]}x{TILE_DENSE[0][1]}-{nt}' for nt in TILE_DENSE_NT] + \
+    [f'tile-{ny}x{nx}-{nt}-mask' for (ny, nx), nt in TILE_MASKED]
 
 
 def host_case(name):
     """(host, A, b, blocks) of a GPU case's system formed on the host: A weighted and row-selected,
     b = the weighted, selected rhs, blocks = block_list of the node blocks.  t64-mf, t64-csr, t64-x0
-    and jacobi run on t64's system."""
-    if name.startswith('ksweep'):
-        shape, nt = name.split('-')[1:]
+    and jacobi run on t64's system; a name that ends in -mask has mask_and_weights applied."""
+    if name.startswith(('ksweep', 'tile')):
+        shape, nt = name.split('-')[1:3]
         shape = tuple(int(v) for v in shape.split('x'))
-        h = ksweep_host(shape, dict(KSWEEP)[shape], int(nt))
+        h = ksweep_host(shape, dict(KSWEEP + TILE_SWEEP + [TILE_DENSE])[shape], int(nt))
     elif name == 'sf3d':
         h = golden_host('sf3d')
     else:
         h = synthetic_host(name if name in ('t15', 't64z') else 't64')
-    w, mask = mask_and_weights(h) if name == 't64-mask' else (h.w, np.ones(h.w.size, bool))
+    w, mask = mask_and_weights(h) if name.endswith('-mask') else (h.w, np.ones(h.w.size, bool))
     A, b = h.A(w, mask), (w * h.rhs)[mask]
     if name == 'priors':
         csr, wx, prior = frame_priors(h, h.S['grids']['dz'].shape[2] // 2)
