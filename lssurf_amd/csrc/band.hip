@@ -1099,6 +1099,7 @@ void band_launch_bsub(System& S, const double* v, int scale_mode, double* out) {
     hipLaunchKernelGGL(k_band_bsub, dim3(nw), dim3(BLOCK), sizeof(double) * TB * (F.w + 1), S.stream, F.R.p, F.D.p,
                        F.T, F.w, F.n, v, S.st.p, scale_mode, F.sc.p, F.perm.p, out, F.part.p,
                        reinterpret_cast<GridBar*>(F.bar.p));
+    KERNEL_CHECK();   // a rejected launch (the ring is dynamic LDS) raises instead of leaving `out` unsolved
 }
 
 void band_launch_fsub(System& S, const double* t, const double* vin, double* vout, double* part) {
@@ -1109,6 +1110,7 @@ void band_launch_fsub(System& S, const double* t, const double* vin, double* vou
     hipLaunchKernelGGL(k_band_fsub, dim3(nw), dim3(BLOCK), sizeof(double) * TB * (F.w + 1), S.stream, F.R.p, F.D.p,
                        F.T, F.w, F.n, t, S.st.p, vin, vout, F.sc.p, F.perm.p, F.part.p, part,
                        reinterpret_cast<GridBar*>(F.bar.p));
+    KERNEL_CHECK();
 }
 
 void band_launch_warm(System& S, const double* x0, double* y0) {

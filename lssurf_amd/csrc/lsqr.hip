@@ -722,7 +722,14 @@ void run_batch(System& S, int count, bool use_graph, int precond, bool mf) {
             c.exec = nullptr;
             hipGraph_t graph;
             HIP_CHECK(hipStreamBeginCapture(S.stream, hipStreamCaptureModeThreadLocal));
-            for (int i = 0; i < count; ++i) launch_any(S, g, i & 1, precond, mf);
+            try {
+                for (int i = 0; i < count; ++i) launch_any(S, g, i & 1, precond, mf);
+            } catch (...) {   // a refused launch (band_launch_*): leave the stream usable
+                graph = nullptr;
+                (void)hipStreamEndCapture(S.stream, &graph);
+                if (graph) (void)hipGraphDestroy(graph);
+                throw;
+            }
             HIP_CHECK(hipStreamEndCapture(S.stream, &graph));
             HIP_CHECK(hipGraphInstantiate(&c.exec, graph, nullptr, nullptr, 0));
             HIP_CHECK(hipGraphDestroy(graph));
