@@ -323,6 +323,41 @@ int lsq_cov_band_bordered(lsq_handle* h, const int32_t* perm, int64_t n_border, 
                           const int64_t* op_ptr, const int32_t* op_col, const double* op_val, double* op_err,
                           int64_t* info);
 
+/* The border term of compute_E where no band factor of the whole system fits (the tiled windows of
+ * lsq_cov_band_windows, lssurf_amd/errors.py): Z = N⁻¹Bᵗ by k CGNR solves instead of the band factor.
+ * The handle holds the GRID-ONLY structured system A_g with its current row weights and row mask
+ * (W = weight × mask); the k border columns are passed here: B over the data rows as CSC (colptr[k+1],
+ * rows strictly increasing within a column, vals UNWEIGHTED: W applies to these rows as to A_g's) and
+ * c_con (k × k, row-major), the already weighted share of C from rows that touch border columns only
+ * (smooth_fit's bias and slope constraint rows).  With N = A_gᵀW²A_g and C = BᵗW²B + c_con:
+ *   z_j = argmin ‖W(A_g x − b_j)‖ = N⁻¹A_gᵀW²b_j        one lsq_solve-like CGNR solve per column, from x = 0,
+ *                                                       with the options o (method 1; precond 1, 3 or 4)
+ *   T = BᵗW²(A_d Z),  S = C − ½(T + Tᵀ),  S̃ = s_k S s_k = R̃ᵀR̃  (s_k = diag(C)^-½; dense.hip's tile kernels)
+ *   var_add[j]    = ‖(Z s_k R̃⁻¹)_j·‖²     per compact column (n): add to the grid-only (N⁻¹)_jj
+ *   var_border[j] = s_k[j]²‖(R̃⁻¹)_j·‖²     the border columns' variances (k)
+ *   op_add[i]     = ‖(op_i Z) s_k R̃⁻¹‖²    per op row (compact columns, as lsq_cov_band): add to op_i N⁻¹ op_iᵀ
+ * The row scales, the block factors or the multigrid levels and the ‖A‖ estimate are set up once for
+ * all k solves.  Z (n_pad × k_pad, column-major; n_pad, k_pad = n, k rounded up to 64) stays on the
+ * device, V = Z s_k R̃⁻¹ is never stored (f64 MFMA over 64-row panels of Z), and every sum has one
+ * fixed order without atomics: a second call returns the same bits.
+ * Returns -1 when a column's solve ends without istop 1 or 2 (the message names the column; a column
+ * without a kept row stops at once with z_j = 0 and counts as solved); no output is written then.
+ * -2: a bias, slope or sensor-grid elimination is set on the handle, the handle is a rank of a
+ * group, there is no CGNR operator for o->precond (see lsq_cg_available), a malformed border or op
+ * row, or S is not positive definite (as lsq_cov_band_bordered).  -5 before anything is allocated:
+ * more than LSQ_BORDER_MAX columns, or n_pad·k_pad·8 + 3·k_pad²·8 bytes exceed 0.8 of the free device
+ * memory beside the solver's buffers (the message names the largest k that fits; LSQ_BSOLVE_BUDGET,
+ * a byte count read per call, overrides the budget for tests).  The handle stays usable after
+ * every error.  info (nullable, 12 doubles): k_pad, device bytes, total and largest CG iterations
+ * of a column, µs of the solves, of T, of S and its factor, of var_add, of op_add (host wall clock,
+ * stream synchronised), asym = max_ij |T_ij − T_ji| s_i s_j (0 for exact solves: a free run-time
+ * measure of their accuracy), the smallest pivot of S̃ (asym / pivot bounds what the solves' error
+ * does to S̃⁻¹), µs of the var_add kernel alone (device events). */
+int lsq_cov_border_solved(lsq_handle* h, int64_t k, const int64_t* colptr, const int32_t* rows, const double* vals,
+                          const double* c_con, const lsq_opts* o, int64_t n_ops, const int64_t* op_ptr,
+                          const int32_t* op_col, const double* op_val, double* var_add, double* var_border,
+                          double* op_add, double* info);
+
 /* The same for a WINDOW of the columns (compute_E at scale, lssurf_amd/errors.py method 'window'):
  * perm[0..n_win) lists the window's compact columns in a banded order; the principal submatrix
  * (AᵀA)_WW = A_WᵀA_W (the other columns held fixed) is factored and E[j] = sqrt(((AᵀA)_WW⁻¹)_jj)

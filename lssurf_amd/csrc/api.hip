@@ -40,6 +40,9 @@ void lsqr_profile(System& S, int reps, int op, double* out);
 void lsqr_sigma_x(System& S, double* h_E);
 void lsqr_get_rinv(System& S, double* h_Ri);
 void graph_cache_drop(const System* S);
+int cov_border_solved(System& S, int64_t k, const int64_t* h_cp, const int32_t* h_rows, const double* h_vals,
+                      const double* h_ccon, const lsq_opts& o, int64_t nops, const int64_t* h_rp, const int32_t* h_ci,
+                      const double* h_v, double* h_var_add, double* h_var_border, double* h_op_add, double* info);
 void form_from_stencils(System& S, int64_t m, int64_t n_full, int32_t n_grids, const lsq_grid_desc* grids,
                         int32_t n_interp, const int32_t* interp_grid, int64_t npts, const double* py,
                         const double* px, const double* pt, int32_t n_stencil, const lsq_stencil_desc* st);
@@ -923,6 +926,26 @@ int lsq_cov_band_bordered(lsq_handle* h, const int32_t* perm, int64_t n_border, 
         if (!perm) return fail(S, "lsq_cov_band_bordered: a border needs perm");
         lsq::band_cov_bordered(S, perm, n_border, E, n_ops, op_ptr, op_col, op_val, op_err, info);
         return 0;
+    });
+}
+
+int lsq_cov_border_solved(lsq_handle* h, int64_t k, const int64_t* colptr, const int32_t* rows, const double* vals,
+                          const double* c_con, const lsq_opts* o, int64_t n_ops, const int64_t* op_ptr,
+                          const int32_t* op_col, const double* op_val, double* var_add, double* var_border,
+                          double* op_add, double* info) {
+    return guarded(h, [&](lsq::System& S) {
+        if (!S.G.rp.p) return fail(S, "lsq_cov_border_solved: no matrix");
+        if (k < 1 || !colptr || !c_con || (colptr[k] > 0 && (!rows || !vals)))
+            return fail(S, "lsq_cov_border_solved: null or empty border");
+        if (!var_add || !var_border) return fail(S, "lsq_cov_border_solved: null output");
+        if (n_ops < 0 || (n_ops > 0 && (!op_ptr || !op_add || (op_ptr[n_ops] > 0 && (!op_col || !op_val)))))
+            return fail(S, "lsq_cov_border_solved: bad op rows");
+        lsq_opts d;
+        lsq_default_opts(&d);
+        d.method = 1;
+        d.precond = 3;
+        return lsq::cov_border_solved(S, k, colptr, rows, vals, c_con, o ? *o : d, n_ops, op_ptr, op_col, op_val, var_add,
+                                      var_border, op_add, info);
     });
 }
 

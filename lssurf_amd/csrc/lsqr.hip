@@ -1025,6 +1025,8 @@ void lsqr_get_rinv(System& S, double* h_Ri) {
 
 #include "lsqr_cg.inc"
 
+#include "bsolve.inc"
+
 #include "lsqr_dist.inc"
 
 #include "lsqr_cg_dist.inc"

@@ -2213,13 +2213,15 @@ struct SetupTrace {
     }
 };
 
-void cg_init(System& S, const double* h_b, const double* h_x0, const lsq_opts& o, int precond, bool no_stop) {
+// dbp: b on the device, all m rows in the caller's row order (rows past o.b_rows zero when that is
+// set).  setup = false: the multigrid levels were set up by an earlier solve with these row weights
+// and mask (lsq_cov_border_solved's later columns); they do not depend on b.
+void cg_init_dev(System& S, const double* dbp, const double* h_x0, const lsq_opts& o, int precond, bool no_stop,
+                 bool setup, SetupTrace& tr) {
     hipStream_t st = S.stream;
-    SetupTrace tr;
     const Grids lg = grids_for(S);
     const CgGrids g = cg_grids(S, precond);
     const int64_t n = S.G.n;
-    const double* dbp = upload_rhs(S, h_b, o, st);
     S.cg_x.zero(st);
     S.cg_z.zero(st);
     for (auto& b : S.cg_pb) b.zero(st);
@@ -2306,7 +2308,7 @@ void cg_init(System& S, const double* h_b, const double* h_x0, const lsq_opts& o
                            S.part_b.p, lg.gD + lg.gS + nbk + nxk, nullptr);
     }
     tr.mark(st, "s0 = A'(Wb-Ax0)");
-    if (precond == 4) {   // multigrid set-up for these row weights (uses q as scratch)
+    if (precond == 4 && setup) {   // multigrid set-up for these row weights (uses q as scratch)
         mg_setup(S);
         S.cg_q.zero(st);
         tr.mark(st, "mg_setup");
@@ -2317,6 +2319,12 @@ void cg_init(System& S, const double* h_b, const double* h_x0, const lsq_opts& o
     HIP_CHECK(hipStreamSynchronize(st));
     tr.mark(st, "z0 = M^-1 s0");
     S.cg_parity = 0;
+}
+
+void cg_init(System& S, const double* h_b, const double* h_x0, const lsq_opts& o, int precond, bool no_stop) {
+    SetupTrace tr;
+    const double* dbp = upload_rhs(S, h_b, o, S.stream);
+    cg_init_dev(S, dbp, h_x0, o, precond, no_stop, true, tr);
 }
 
 // capture + instantiate the graph of `count` (a multiple of CG_XK) iterations from the current

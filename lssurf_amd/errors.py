@@ -30,6 +30,12 @@ With data or slope biases (a non-empty bias_model) the bias columns couple every
 cross: 'band' orders them last (`bordered_band_order`) as the dense border of
 `lsq_cov_band_bordered` (csrc/border.inc), 'dense' takes them as ordinary columns, 'window' has no
 place for them and is refused; E gains sigma_bias / sigma_slope_bias (smooth_fit.py:274).
+
+`border_solve=True` (smooth_fit's lsq_E_border_solve) gives 'window' its place for them: the windows
+run on the grid-only system (`split_border`), which yields (N⁻¹)_jj, and the border's share
+var_add = ‖(N⁻¹Bᵗ R_S⁻¹)_j·‖² comes from one CGNR solve of that system per border column
+(`lsq_cov_border_solved`, csrc/bsolve.inc) — the formula of border.inc with the band factor's
+N⁻¹Bᵗ replaced by solves, so it reaches the sizes where no band factor fits.
 """
 import os
 from time import time
@@ -260,29 +266,184 @@ def _grid_values(op, vals):
     return E[grid.col_0:grid.col_N].reshape(grid.shape)
 
 
+def _triplet_op(r, c, v, n_eq, col_N, name):
+    """A generic lin_op (no structure records) from triplets."""
+    from .lin_op import lin_op
+    op = lin_op(None, col_N=col_N, col_0=0, name=name)
+    op._r, op._c, op._v = np.asarray(r, int), np.asarray(c, int), np.asarray(v, float)
+    op.N_eq = int(n_eq)
+    op.parts = None
+    op.shape = (op.N_eq, col_N)
+    return op
+
+
+def split_border(G_data, Gc, Ec, keep_cols, n_grid, grid_ops=None):
+    """The fit objects of a system with bias (and slope-bias) columns behind the n_grid grid columns,
+    split for lsq_cov_border_solved: (G_grid, Gc_grid, B, c_con).
+
+    The grid-only constraint rows are a prefix of Gc (smooth_fit._bias_fit_system: the bias and slope
+    constraint rows are its last rows); every row behind them must touch border columns only.
+    G_grid, Gc_grid: the operators over the grid columns — the data rows without their border entries
+    and that prefix.  grid_ops = (G_grid, Gc_grid) as smooth_fit built them (with their structure
+    records, which the combined operators have lost; checked against the split's sizes) are returned
+    as they are; without them generic operators are made from the triplets.
+    B: the border block of the data rows, CSC (data rows × k, unweighted), one column per kept column
+    at or beyond n_grid, ascending.  c_con (k × k): Σ w_r² g_rᵀg_r over the border-only rows r of Gc
+    with w = 1 / Ec, the share of the border block that no data row carries."""
+    keep_cols = np.asarray(keep_cols)
+    n_grid = int(n_grid)
+    border_cols = keep_cols[keep_cols >= n_grid]
+    k = int(border_cols.size)
+    pos = np.full(int(Gc.col_N) - n_grid, -1, np.int64)   # full border column -> border index (removed: -1)
+    pos[border_cols - n_grid] = np.arange(k)
+    r, c, v = G_data.triplets()
+    r, c, v = r[v != 0], c[v != 0], v[v != 0]   # zero entries are no entries (lin_op.toCSR)
+    on = c >= n_grid
+    kept = pos[c[on] - n_grid]
+    B = sp.csc_matrix((v[on][kept >= 0], (r[on][kept >= 0], kept[kept >= 0])), shape=(int(G_data.N_eq), k))
+    B.sum_duplicates()
+    B.sort_indices()
+    # a stacked Gc (lin_op.vstack) names its operators: those whose columns end at or below n_grid hold
+    # no border column, so only the few operators behind them are read (Gc has 7·10⁷ rows at C4)
+    tail = []
+    stacked = list(getattr(Gc, 'stacked', None) or ())
+    have_ops = grid_ops is not None and grid_ops[0] is not None and grid_ops[1] is not None
+    if have_ops and stacked and sum(int(op.N_eq) for op, _ in stacked) == int(Gc.N_eq):
+        while stacked and int(stacked[-1][0].col_N) > n_grid:
+            tail.insert(0, stacked.pop())
+    if tail and all(int(op.col_N) <= n_grid for op, _ in stacked):
+        parts = [(op.triplets(), off) for op, off in tail]
+        rc = np.concatenate([t[0] + off for t, off in parts])
+        cc, vc = np.concatenate([t[1] for t, _ in parts]), np.concatenate([t[2] for t, _ in parts])
+        first_tail = int(tail[0][1])
+    else:
+        rc, cc, vc = Gc.triplets()
+        first_tail = None
+    rc, cc, vc = rc[vc != 0], cc[vc != 0], vc[vc != 0]
+    onc = cc >= n_grid
+    border_rows = np.unique(rc[onc])
+    n_cg = int(border_rows[0]) if border_rows.size else int(Gc.N_eq)
+    if first_tail is not None:
+        n_cg = first_tail if border_rows.size else int(Gc.N_eq)
+    if np.any(rc[~onc] >= n_cg):
+        raise ValueError('split_border: a constraint row at or behind the first bias constraint row holds a grid '
+                         'column; the grid-only constraint rows must be a prefix of Gc')
+    keptc = pos[cc[onc] - n_grid]
+    w = 1. / np.asarray(Ec, float)
+    Cb = sp.csr_matrix((vc[onc][keptc >= 0] * w[rc[onc][keptc >= 0]], (rc[onc][keptc >= 0], keptc[keptc >= 0])),
+                       shape=(int(Gc.N_eq), k))
+    c_con = np.asarray((Cb.T @ Cb).todense(), float)
+    if have_ops:
+        G_grid, Gc_grid = grid_ops
+        if int(G_grid.N_eq) != int(G_data.N_eq) or int(Gc_grid.N_eq) != n_cg or int(Gc_grid.col_N) != n_grid:
+            raise ValueError('split_border: grid_ops are not the grid-only operators of these fit objects')
+    else:
+        G_grid = _triplet_op(r[~on], c[~on], v[~on], G_data.N_eq, n_grid, 'G_grid')
+        Gc_grid = _triplet_op(rc[~onc], cc[~onc], vc[~onc], n_cg, n_grid, 'constraints')
+    return G_grid, Gc_grid, B, c_con
+
+
 WINDOW_BORDER_REFUSAL = ("compute_E with bias_params: lsq_E_method='window' has no place for a bias column — a "
                          "conditional-variance window holds the columns outside it fixed, and a bias column couples "
                          "the whole tile; use 'band' (at most WINDOW_MIN_COLS columns) or 'dense'")
 
 
+def _window_with_margin(solver, grids, keep_cols, op, timing):
+    """window_cov with the margin-doubling self-check: (E, op errors, check, tile, margin)."""
+    # LSQ_E_TILE / LSQ_E_MARGIN: development overrides (A/B of the window geometry)
+    tile = int(os.environ.get('LSQ_E_TILE', WINDOW_TILE))
+    margin = m0 = int(os.environ.get('LSQ_E_MARGIN', WINDOW_MARGIN))
+    while True:
+        E0c, errs, check = window_cov(solver, grids, keep_cols, op, tile=tile, margin=margin, timing=timing)
+        if check <= WINDOW_CHECK_TOL or margin >= 4 * m0:
+            break
+        print(f'calc_and_parse_errors: window sigma moved by {check:.1e} with twice the margin '
+              f'({margin} nodes); retrying with a margin of {2 * margin}', flush=True)
+        margin *= 2
+    if check > WINDOW_CHECK_TOL:
+        print(f'calc_and_parse_errors: WARNING window sigma within {check:.1e} only (margin {margin} nodes)',
+              flush=True)
+    return E0c, errs, check, tile, margin
+
+
+def _window_border_solved(G_data, Gc, Ec, w, in_TSE, keep_cols, grids, n_grid, avg_ops, device, timing, grid_ops,
+                          fit_args):
+    """(E0c over every compact column, {key: op errors}, approx) of a system with bias columns by
+    windows on the grid-only system plus lsq_cov_border_solved (module docstring)."""
+    from .smooth_fit import DEFAULTS, _solve_opts
+    G_grid, Gc_grid, B, c_con = split_border(G_data, Gc, Ec, keep_cols, n_grid, grid_ops)
+    keep_g = keep_cols[keep_cols < n_grid]
+    fs = FitSystem(G_grid, Gc_grid, keep_g, n_grid, device=device, grids=grids)
+    try:
+        n_rows = fs.n_data + fs.n_con          # the grid-only rows are a prefix of the caller's rows
+        wg = np.ascontiguousarray(w[:n_rows])
+        fs.solver.set_row_weight(wg)
+        fs.solver.set_row_mask(np.concatenate([np.asarray(in_TSE, bool), np.ones(fs.n_con, bool)]))
+        keys = list(avg_ops)
+        mats = [_compact_rows(avg_ops[k], keep_g, n_grid) for k in keys]
+        op = sp.vstack(mats).tocsr() if mats else None
+        E0g, errs, check, tile, margin = _window_with_margin(fs.solver, grids, keep_g, op, timing)
+        # the fit's own solver options (smooth_fit._solve_opts); only CGNR carries the call, so never the
+        # dense preconditioner of small systems
+        args = dict(DEFAULTS)
+        args.update(fit_args or {})
+        mg = args['lsq_precond'] == 'auto' and fs.multigrid_available()
+        opts = _solve_opts(args, keep_g.size, fs.has_blocks, mg, dense_ok=False)
+        tic = time()
+        var_add, var_border, op_add, info = fs.solver.cov_border_solved(B, c_con, op, **opts)
+    finally:
+        fs.close()
+    amp = info['asym'] / info['min_pivot'] if info['min_pivot'] > 0 else np.inf
+    if amp > WINDOW_CHECK_TOL:
+        print(f"calc_and_parse_errors: WARNING the border solves leave T = B N^-1 B' asymmetric by {info['asym']:.1e} "
+              f"against a smallest pivot of {info['min_pivot']:.1e} ({amp:.1e}); tighten lsq_atol / lsq_btol",
+              flush=True)
+    timing['E_border_solved'] = {'k': int(B.shape[1]), 'iters': info['iters'], 'iters_max': info['iters_max'],
+                                 'time_s': time() - tic, 'solve_s': info['solve_us'] * 1e-6,
+                                 'border_s': (info['T_us'] + info['S_us'] + info['var_add_us'] + info['op_add_us']) * 1e-6,
+                                 'bytes': info['bytes'], 'asym': info['asym'], 'min_pivot': info['min_pivot'],
+                                 'precond': int(opts['precond'])}
+    approx = (f'window (conditional variance): tile {tile}, margin {margin} nodes, self-check {check:.1e} relative '
+              f"at twice the margin; border of {B.shape[1]} columns by CGNR solves (asym {info['asym']:.1e}, "
+              f"pivot {info['min_pivot']:.1e})")
+    E0c = np.concatenate((np.sqrt(E0g ** 2 + var_add), np.sqrt(var_border)))
+    op_err, off = {}, 0
+    for k, m in zip(keys, mats):
+        op_err[k] = np.sqrt(errs[off:off + m.shape[0]] ** 2 + op_add[off:off + m.shape[0]])
+        off += m.shape[0]
+    return E0c, op_err, approx
+
+
 def calc_and_parse_errors(E, G_data, Gc, Ed, Ec, data, in_TSE, keep_cols, grids, avg_ops, device=0, timing=None,
-                          method='auto', bias_model=None, bias_params=None):
+                          method='auto', bias_model=None, bias_params=None, border_solve=False, grid_ops=None,
+                          fit_args=None):
     """With a non-empty bias_model the system holds the bias (and slope-bias) columns behind the
     grids': 'band' takes them as the border of lsq_cov_band_bordered, 'dense' as ordinary columns,
-    and E gains sigma_bias / sigma_slope_bias (smooth_fit.py:274)."""
+    and E gains sigma_bias / sigma_slope_bias (smooth_fit.py:274).  border_solve=True: 'window' (and
+    'auto' above WINDOW_MIN_COLS columns) runs with them — windows on the grid-only system plus
+    lsq_cov_border_solved; grid_ops = smooth_fit's structured grid-only operators (split_border) and
+    fit_args = its solver keys (lsq_atol, lsq_btol, lsq_conlim, lsq_precond, …: smooth_fit._solve_opts)."""
     timing = {} if timing is None else timing
     if bias_model:
         if method == 'auto' and keep_cols.size > WINDOW_MIN_COLS:
             method = 'window'
-        if method == 'window':
+        if method == 'window' and not border_solve:
             raise NotImplementedError('calc_and_parse_errors: ' + WINDOW_BORDER_REFUSAL)
     tic = time()
     approx = None   # window method: how σ was approximated (attached to the output grids)
     sigma_data = np.sqrt(Ed ** 2 + data.sigma_extra ** 2)
     E_all = np.concatenate((sigma_data, Ec))
     w = 1. / E_all                                   # TCinv, smooth_fit.py:697
-    fs = FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=device)
     op_err = {}
+    if bias_model and method == 'window':   # border_solve: the bias columns beside the windows
+        n_grid = max(int(g.col_N) for g in grids.values() if getattr(g, 'N_dims', 0) >= 2)
+        E0c, op_err, approx = _window_border_solved(G_data, Gc, Ec, w, in_TSE, keep_cols, grids, n_grid, avg_ops,
+                                                    device, timing, grid_ops, fit_args)
+        timing['decompose_qz'] = time() - tic
+        Rinv = None
+        return _parse_errors(E, E0c, Rinv, op_err, approx, Gc, keep_cols, grids, avg_ops, timing, tic, bias_model,
+                             bias_params, data)
+    fs = FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=device)
     try:
         fs.solver.set_row_weight(w)
         fs.solver.set_row_mask(np.concatenate([np.asarray(in_TSE, bool), np.ones(Gc.N_eq, bool)]))
@@ -292,20 +453,7 @@ def calc_and_parse_errors(E, G_data, Gc, Ed, Ec, data, in_TSE, keep_cols, grids,
             keys = list(avg_ops)
             mats = [_compact_rows(avg_ops[k], keep_cols, Gc.col_N) for k in keys]
             op = sp.vstack(mats).tocsr() if mats else None
-            # LSQ_E_TILE / LSQ_E_MARGIN: development overrides (A/B of the window geometry)
-            tile = int(os.environ.get('LSQ_E_TILE', WINDOW_TILE))
-            margin = m0 = int(os.environ.get('LSQ_E_MARGIN', WINDOW_MARGIN))
-            while True:
-                E0c, errs, check = window_cov(fs.solver, grids, keep_cols, op, tile=tile, margin=margin,
-                                              timing=timing)
-                if check <= WINDOW_CHECK_TOL or margin >= 4 * m0:
-                    break
-                print(f'calc_and_parse_errors: window sigma moved by {check:.1e} with twice the margin '
-                      f'({margin} nodes); retrying with a margin of {2 * margin}', flush=True)
-                margin *= 2
-            if check > WINDOW_CHECK_TOL:
-                print(f'calc_and_parse_errors: WARNING window sigma within {check:.1e} only (margin {margin} nodes)',
-                      flush=True)
+            E0c, errs, check, tile, margin = _window_with_margin(fs.solver, grids, keep_cols, op, timing)
             approx = (f'window (conditional variance): tile {tile}, margin {margin} nodes, '
                       f'self-check {check:.1e} relative at twice the margin')
             timing['decompose_qz'] = time() - tic
@@ -342,6 +490,13 @@ def calc_and_parse_errors(E, G_data, Gc, Ed, Ec, data, in_TSE, keep_cols, grids,
             raise ValueError(f'calc_and_parse_errors: unknown method {method!r}')
     finally:
         fs.close()
+    return _parse_errors(E, E0c, Rinv, op_err, approx, Gc, keep_cols, grids, avg_ops, timing, tic, bias_model,
+                         bias_params, data)
+
+
+def _parse_errors(E, E0c, Rinv, op_err, approx, Gc, keep_cols, grids, avg_ops, timing, tic, bias_model, bias_params,
+                  data):
+    """E0c (σ per compact column) and the op errors onto the output grids (smooth_fit.py:253-274)."""
     timing['propagate_errors'] = time() - tic
     E0 = np.zeros(Gc.col_N)
     E0[keep_cols] = E0c

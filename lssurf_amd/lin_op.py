@@ -511,6 +511,7 @@ class lin_op:
                     np.concatenate([np.ravel(op.v) for op, _ in offsets]),
                     np.concatenate([op.ind0 for op in ops]))
         self._lazy = build
+        self.stacked = tuple(offsets)   # (operator, first row) in row order: errors.split_border reads the last ones
         if ee:
             self.expected = np.concatenate(ee)
         if self.name is not None and len(self.name) > 0:

@@ -31,7 +31,11 @@ or 'auto' (with priors: 'columns', with a warning where it would have eliminated
 compute_E with bias_params (and data_slope_sensors) runs when lsq_E_border=True: the bias columns are
 the dense border of a bordered band factor (lsq_cov_band_bordered) and E gains sigma_bias /
 sigma_slope_bias; without the key it raises NotImplementedError, as do lsq_E_method='window', sensor
-bias grids, priors and n_gpus > 1 with it.
+bias grids, priors and n_gpus > 1 with it.  lsq_E_border_solve=True (with lsq_E_border=True) lets
+lsq_E_method='window', and 'auto' above errors.WINDOW_MIN_COLS columns, run with the biases: tiled
+windows on the grid-only system plus one CGNR solve per bias column (lsq_cov_border_solved,
+errors.calc_and_parse_errors); 'band' and 'dense' are unchanged, and sensor bias grids, priors and
+n_gpus > 1 stay refused.
 """
 from time import ctime, time
 
@@ -78,6 +82,8 @@ DEFAULTS = {'reference_epoch': 0, 'W_ctr': 1e4, 'return_fit_objects': False, 'ma
             # priors (prior_args / prior_edge_args) inside the multigrid preconditioner: their rows
             # lumped into its coarse levels (opt-in; without priors the key does nothing)
             'lsq_prior_mg': False, 'lsq_E_border': False,
+            # compute_E with biases at window scale: the border by CGNR solves (acts with lsq_E_border only)
+            'lsq_E_border_solve': False,
             # sensor bias grids beside bias_params / data_slope_sensors eliminated jointly (opt-in; the
             # bias IDs and slope groups must nest in the grids' sensors, as with 'sensor' in bias_params)
             'lsq_sgrid_joint': False}
@@ -826,6 +832,8 @@ def smooth_fit(**kwargs):
         raise ValueError(f"smooth_fit: lsq_prior_mg must be True or False, not {args['lsq_prior_mg']!r}")
     if not isinstance(args['lsq_E_border'], (bool, np.bool_)):
         raise ValueError(f"smooth_fit: lsq_E_border must be True or False, not {args['lsq_E_border']!r}")
+    if not isinstance(args['lsq_E_border_solve'], (bool, np.bool_)):
+        raise ValueError(f"smooth_fit: lsq_E_border_solve must be True or False, not {args['lsq_E_border_solve']!r}")
     if not isinstance(args['lsq_sgrid_joint'], (bool, np.bool_)):
         raise ValueError(f"smooth_fit: lsq_sgrid_joint must be True or False, not {args['lsq_sgrid_joint']!r}")
     bias_mode = args['lsq_bias']
@@ -837,7 +845,7 @@ def smooth_fit(**kwargs):
             raise ValueError(f"smooth_fit: lsq_bias must be 'eliminate', 'columns' or 'auto', not {bias_mode!r}")
         if args['compute_E'] and not args['lsq_E_border']:
             raise NotImplementedError("smooth_fit: compute_E with bias_params (sigma_bias) is outside lssurf_amd")
-        if args['compute_E'] and args['lsq_E_method'] == 'window':
+        if args['compute_E'] and args['lsq_E_method'] == 'window' and not args['lsq_E_border_solve']:
             from .errors import WINDOW_BORDER_REFUSAL
             raise NotImplementedError('smooth_fit: ' + WINDOW_BORDER_REFUSAL)
         if int(args['n_gpus']) > 1 or (args['devices'] is not None and len(args['devices']) > 1):
@@ -947,7 +955,8 @@ def smooth_fit(**kwargs):
     bias_model, G_grid, Gc_grid = {}, None, None
     if args['bias_params'] is not None:
         data, bias_model = assign_bias_ID(data, args['bias_params'], bias_filter=args['bias_filter'])
-        if bias_mode != 'columns':
+        # (also what compute_E's border solves run on: errors.split_border)
+        if bias_mode != 'columns' or (args['compute_E'] and args['lsq_E_border_solve']):
             G_grid = interp_ops()
             Gc_grid = lin_op(None, name='constraints').vstack(list(constraint_op_list))
         setup_bias_fit(data, bias_model, G_data, constraint_op_list, bias_param_name='bias_ID')
@@ -1128,7 +1137,10 @@ def smooth_fit(**kwargs):
                 tic_error = time()
             calc_and_parse_errors(E, G_data, Gc, Ed, Ec(), data, in_TSE, keep_cols, grids, averaging_ops,
                                   device=args['device'], timing=timing, method=args['lsq_E_method'],
-                                  bias_model=bias_model, bias_params=args['bias_params'])
+                                  bias_model=bias_model, bias_params=args['bias_params'],
+                                  border_solve=bool(args['lsq_E_border_solve']) and bool(bias_model),
+                                  grid_ops=(G_grid, Gc_grid) if bias_model and not has_sgrids else None,
+                                  fit_args=args)
             if args['VERBOSE']:
                 print('\tUncertainty propagation took %3.2f seconds' % (time() - tic_error), flush=True)
     finally:

@@ -486,6 +486,46 @@ class LSQSolver:
                                                   ptr(ci), ptr(v), ptr(out), ptr(info)), 'lsq_cov_band_bordered')
         return E, out, info
 
+    BORDER_SOLVED_INFO = ('k_pad', 'bytes', 'iters', 'iters_max', 'solve_us', 'T_us', 'S_us', 'var_add_us',
+                          'op_add_us', 'asym', 'min_pivot', 'var_add_kernel_us')
+
+    def cov_border_solved(self, B, c_con, op=None, atol=1e-10, btol=1e-10, conlim=1e8, maxit=0, precond=3, batch=0,
+                          use_graph=True, anorm0=0.0, **_ignored):
+        """The border term of the error propagation without a band factor (lsq_cov_border_solved):
+        this handle holds the grid-only system with its weights and mask, B (data rows × k, unweighted)
+        the border columns of the data rows, c_con (k × k) the weighted share of the border block from
+        rows that touch border columns only.  One CGNR solve per border column with the given options
+        (precond 1, 3 or 4).  Returns (var_add per compact column, var_border per border column,
+        op_add per row of `op` or None, info dict): var(grid column j) = (N⁻¹)_jj + var_add[j],
+        var(op row) = op N⁻¹ opᵀ + op_add, var(border column) = var_border."""
+        B = sp.csc_matrix(B)
+        B.sort_indices()
+        k = B.shape[1]
+        cc = as_c(c_con, np.float64)
+        if cc.shape != (k, k):
+            raise ValueError(f'cov_border_solved: c_con must be {k} x {k}')
+        cp, rows, vals = as_c(B.indptr, np.int64), as_c(B.indices, np.int32), as_c(B.data, np.float64)
+        o = default_opts(atol=atol, btol=btol, conlim=conlim, maxit=int(maxit), precond=int(precond), use_x0=0,
+                         batch=int(batch), use_graph=int(bool(use_graph)), method=1, anorm0=float(anorm0))
+        var_add, var_border, info = np.zeros(self.n), np.zeros(k), np.zeros(len(self.BORDER_SOLVED_INFO))
+        if op is None or op.shape[0] == 0:
+            n_ops, rp, ci, v, out = 0, None, None, None, None
+        else:
+            op = sp.csr_matrix(op)
+            op.sort_indices()
+            if op.shape[1] != self.n:
+                raise ValueError('cov_border_solved: the op rows run over the compact columns of the handle')
+            n_ops = op.shape[0]
+            rp, ci, v = as_c(op.indptr, np.int64), as_c(op.indices, np.int32), as_c(op.data, np.float64)
+            out = np.zeros(n_ops)
+        self._check(self._L.lsq_cov_border_solved(self._h, k, ptr(cp), ptr(rows), ptr(vals), ptr(cc), ctypes.byref(o),
+                                                  n_ops, ptr(rp), ptr(ci), ptr(v), ptr(var_add), ptr(var_border),
+                                                  ptr(out), ptr(info)), 'lsq_cov_border_solved')
+        d = dict(zip(self.BORDER_SOLVED_INFO, info.tolist()))
+        for key in ('k_pad', 'bytes', 'iters', 'iters_max'):
+            d[key] = int(d[key])
+        return var_add, var_border, out, d
+
     def cov_band_window(self, perm_w, op=None, inner=None):
         """cov_band for a window W of the columns (perm_w: its compact columns in a banded order):
         E[j] = sqrt(((A_WᵀA_W)⁻¹)_jj) in WINDOW order (len(perm_w) entries) and the op rows' errors,
