@@ -530,11 +530,27 @@ int lsq_profile_kernels(lsq_handle* h, int32_t reps, int32_t op, double* out8);
  * reason is in lsq_last_error).  lsq_profile_cg: per-kernel HIP-event times of one CG iteration,
  * out8 = {ms data rows t = Ad·p, ms normal operator q = N p + Adᵀt, ms update + preconditioner,
  * ms of the two scalar kernels, algorithmic HBM bytes per launch of the first three, mode bits:
- * 1 matrix-free data rows, 2 wave-strip normal kernel, 4 column-mode operator (else tile mode)}.
+ * 1 matrix-free data rows, 2 wave-strip normal kernel, 4 column-mode operator (else tile mode),
+ * 8 chunk mode (tile mode's step on tiles cut along the last grid dimension; bit 4 clear)}.
  * lsq_normal_apply: q = AᵀA p for the current row weights/mask, p and q over the FULL column
  * space (length n_full of lsq_set_col_map; test hook for the normal operator). */
 int lsq_cg_available(lsq_handle* h, int32_t precond);
 int lsq_profile_cg(lsq_handle* h, int32_t reps, int32_t precond, double* out8);
+/* Chunk mode: CGNR on grids of 20 to 64 nodes along their last dimension (epochs), where a
+ * tile-mode image of whole time columns exceeds 64 KB of LDS and method 1 otherwise falls back to
+ * LSQR.  lsq_set_cg_chunks(h, 1) lets the layout cut such a grid's tiles along the last dimension
+ * too (k_cg_normal_chunk); systems that run column or tile mode are laid out and solved exactly as
+ * without it, and what tile mode refuses (multigrid, eliminated biases / slopes / sensor grids,
+ * extra rows, more than 64 nodes) stays refused.  Callable any time after lsq_create; a change
+ * drops the CGNR description, the captured iterations and the multigrid levels, and the next
+ * lsq_cg_available / lsq_solve lays out afresh.  Returns −2 (reason in lsq_last_error) on a rank of
+ * a distributed, virtual or device group.  Default: off.
+ * lsq_cg_layout_info builds the description if needed: out8 = {mode (0 no CGNR operator — the
+ * reason is in lsq_last_error —, 1 column, 2 tile, 3 chunk), rows per tile ty of the grid with the
+ * longest last dimension, its chunk length tc, its chunks per tile, the LDS stride of its node
+ * columns, LDS bytes of the largest tile, workgroups of one normal-operator launch, 0}. */
+int lsq_set_cg_chunks(lsq_handle* h, int32_t on);
+int lsq_cg_layout_info(lsq_handle* h, int64_t* out8);
 /* Multigrid (precond 4) test hooks.  lsq_mg_info: out[0] = levels L, then per level
  * (S0, S1, n_full, removed epoch) — cap must hold 1 + 4L values.  lsq_mg_apply on level l's full
  * column space (z0 grid then dz grid, in the system's order): what 0: y = N_l x (level 0: AᵀA;

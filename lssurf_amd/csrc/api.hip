@@ -14,6 +14,8 @@ bool cg_available(System& S, int precond);
 int cg_solve(System& S, const double* h_b, double* h_x, const lsq_opts& o, lsq_stats* stats);
 int cg_iterate(System& S, const double* h_b, int64_t iters, const lsq_opts& o, lsq_stats* stats);
 void cg_profile(System& S, int reps, int precond, double* out);
+void cg_set_chunks(System& S, bool on);
+void cg_layout_info(System& S, int64_t* out8);
 void cg_profile_xr(System& S, int reps, int precond, double* out);
 void cg_apply_normal(System& S, const double* h_p, double* h_q);
 void cg_data_colsum(System& S, const double* h_f, double* h_out);
@@ -527,6 +529,26 @@ int lsq_profile_cg(lsq_handle* h, int32_t reps, int32_t precond, double* out8) {
         if (!lsq::cg_available(S, precond)) return fail(S, "lsq_profile_cg: CGNR not available: " + S.cg_why);
         lsq::graph_cache_drop(&S);
         lsq::cg_profile(S, reps > 0 ? reps : 10, precond, out8);
+        return 0;
+    });
+}
+
+int lsq_set_cg_chunks(lsq_handle* h, int32_t on) {
+    return guarded(h, [&](lsq::System& S) {
+        if (S.dist || S.virt || S.comm || S.nranks > 1)
+            return fail(S, "lsq_set_cg_chunks: chunk mode is single-GPU; a rank of a distributed, virtual or device "
+                           "group runs the column-mode operator");
+        lsq::cg_set_chunks(S, on != 0);
+        return 0;
+    });
+}
+
+int lsq_cg_layout_info(lsq_handle* h, int64_t* out8) {
+    return guarded(h, [&](lsq::System& S) {
+        if (!S.G.rp.p) return fail(S, "lsq_cg_layout_info: no matrix");
+        if (!out8) return fail(S, "lsq_cg_layout_info: null output");
+        lsq::cg_layout_info(S, out8);
+        if (!out8[0]) S.err = S.cg_why.empty() ? "not a structured single-GPU system" : S.cg_why;
         return 0;
     });
 }

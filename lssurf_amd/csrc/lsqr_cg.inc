@@ -15,6 +15,7 @@
 // One iteration = five launches, scalars on the device:
 //   k_cg_data    t = Ad·p,  p = z + β p_old gathered on the fly           (data rows)
 //   k_cg_normal  p = z + β p_old staged per tile in LDS (written once), q = N p + ATd·t, Σ p·q
+//                (k_cg_normal_chunk where a tile of whole dim-2 columns exceeds LDS: lsq_set_cg_chunks)
 //   k_cg_alpha   α = ρ / pᵀq; Lanczos-derived ‖A‖ and ‖Δx‖ estimates               (1 block)
 //   k_cg_block   x += α p, s −= α q, z = M⁻¹ s (block-Jacobi R_b⁻¹R_b⁻ᵀ, or Jacobi), Σ sᵀz
 //   k_cg_beta    β = ρ'/ρ, ‖r‖² −= α ρ, LSQR stopping rules                         (1 block)
@@ -910,6 +911,147 @@ __global__ __launch_bounds__(BLOCK) void k_cg_normal(const CgState* __restrict__
     store_partial(gam, part, blockIdx.x);
 }
 
+// Chunk mode: k_cg_normal on tiles that are also cut along dim 2 (cg_chunk_geometry), for grids whose
+// whole dim-2 columns do not fit LDS (20 … 64 epochs).  A workgroup is one (tile, chunk), the chunks of
+// a tile on consecutive ids (they share the lines of its columns).  Chunk ck owns t in
+// [ck·S2/nch, (ck + 1)·S2/nch) and stages th more nodes on either side: image index
+// front + (r·wx + xi)·tpad + (t − t0 + th).  Everything staged is z + β p_old — never the new p, which
+// another workgroup may not have written yet — and only the owned (row, x, t) entries are written
+// back as p, enter q and count in pᵀNp.  The partials leave through the same fixed-order sum as tile
+// mode's, one slot per workgroup.
+__global__ __launch_bounds__(BLOCK) void k_cg_normal_chunk(const CgState* __restrict__ st, const CgDesc* __restrict__ cd,
+                                                           const double* __restrict__ coef, const double* __restrict__ z,
+                                                           const double* __restrict__ pold, double* __restrict__ pnew,
+                                                           double* __restrict__ q, const int32_t* __restrict__ arp,
+                                                           const int32_t* __restrict__ aci,
+                                                           const double* __restrict__ aval,
+                                                           const double* __restrict__ td, double* __restrict__ part) {
+    if (st->stop) return;
+    const int tile = cg_tile_of_block();
+    if (tile >= cd->ntiles) {
+        if (threadIdx.x == 0) part[blockIdx.x] = 0.0;
+        return;
+    }
+    int g = 0;
+    while (g + 1 < cd->n_grids && tile >= cd->g[g + 1].tile0) ++g;   // tiles are numbered grid by grid
+    const CgGrid& C = cd->g[g];
+    const int tl = tile - C.tile0;
+    const int tyx = tl / C.nch, ck = tl - tyx * C.nch;
+    const int tyi = tyx / C.ntx;
+    const int y0 = tyi * C.ty, x0 = (tyx - tyi * C.ntx) * CG_TX;
+    const int S0 = C.shape[0], S1 = C.shape[1], S2 = C.shape[2];
+    const int t0 = ck * S2 / C.nch, tlen = (ck + 1) * S2 / C.nch - t0;   // tc or tc − 1 nodes
+    const int hy = C.hy, hx = C.hx, th = C.th, wx = C.wx, tpad = C.tpad, front = C.front;
+    const int64_t col0 = C.col0;
+    const double beta = st->beta;
+    double* L = mf_zl;
+
+    // 1. stage p = z + β p_old over the tile's rows, dim-1 positions and chunk, each with its halo;
+    //    zeros outside the grid, in the padding of a column and in the front / back pads
+    {
+        const int rowlen = wx * tpad, img = (C.ty + 2 * hy) * rowlen, lds = C.lds, tw = tlen + 2 * th;
+        for (int i0 = threadIdx.x; i0 < lds; i0 += CG_SU * BLOCK) {
+            int64_t gi[CG_SU];
+            bool ld[CG_SU], own[CG_SU];
+#pragma unroll
+            for (int k = 0; k < CG_SU; ++k) {
+                const int i = i0 + k * BLOCK, ii = i - front;
+                ld[k] = own[k] = false;
+                gi[k] = 0;
+                if (i < lds && ii >= 0 && ii < img) {
+                    const int r = (int)fdiv((uint32_t)ii, C.fd_row);
+                    const int rem = ii - r * rowlen;
+                    const int xi = (int)fdiv((uint32_t)rem, C.fd_pad);
+                    const int ti = rem - xi * tpad;
+                    const int y = y0 - hy + r, x = x0 - hx + xi, t = t0 - th + ti;
+                    if (ti < tw && t >= 0 && t < S2 && y >= 0 && y < S0 && x >= 0 && x < S1) {
+                        ld[k] = true;
+                        gi[k] = col0 + ((int64_t)y * S1 + x) * S2 + t;
+                        own[k] = r >= hy && r < hy + C.ty && xi >= hx && xi < hx + CG_TX && ti >= th && ti < th + tlen;
+                    }
+                }
+            }
+            double zv[CG_SU], pv[CG_SU];
+#pragma unroll
+            for (int k = 0; k < CG_SU; ++k) {
+                zv[k] = ld[k] ? z[gi[k]] : 0.0;
+                pv[k] = ld[k] ? pold[gi[k]] : 0.0;
+            }
+#pragma unroll
+            for (int k = 0; k < CG_SU; ++k) {
+                const int i = i0 + k * BLOCK;
+                if (i < lds) {
+                    const double v = zv[k] + beta * pv[k];
+                    L[i] = v;
+                    if (own[k]) pnew[gi[k]] = v;
+                }
+            }
+        }
+    }
+    __syncthreads();
+
+    // 2. q = N p + Adᵀt for the chunk's owned nodes, k_cg_normal's scheme: lane = dim-1 position, a
+    //    wave takes (row, t) items wid, wid + 4, ...; the coefficient class of t is that of the
+    //    absolute t; the coefficient row is wave-uniform when the tile is clear of both dim-1 edges
+    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int nitems = C.ty * tlen;   // ≤ 4·CG_MAXI (cg_chunk_geometry)
+    const int x = x0 + lane;
+    const bool xin = x < S1;
+    const int cx = cg_cls(xin ? x : 0, S1, C.K[1], C.ncls[1]);
+    const bool xuni = x0 >= C.K[1] && x0 + CG_TX - 1 <= S1 - 1 - C.K[1];
+    const int noff = C.noff;
+    double qv[CG_MAXI];
+    double gam = 0.0;
+#pragma unroll
+    for (int k = 0; k < CG_MAXI; ++k) {
+        qv[k] = 0.0;
+        const int it = wid + 4 * k;
+        if (it >= nitems) continue;
+        const int tyl = it / tlen, ti = it - tyl * tlen;
+        const int y = y0 + tyl, t = t0 + ti;
+        if (y >= S0) continue;
+        const int cy = cg_cls(y, S0, C.K[0], C.ncls[0]), ct = cg_cls(t, S2, C.K[2], C.ncls[2]);
+        const int center = front + ((tyl + hy) * wx + lane + hx) * tpad + ti + th;
+        double acc = 0.0;
+        if (xuni) {
+            const int rb = __builtin_amdgcn_readfirstlane(C.coef0 + ((cy * C.ncls[1] + C.K[1]) * C.ncls[2] + ct) * noff);
+            const double* __restrict__ cr = coef + rb;
+            for (int o = 0; o < noff; ++o) acc += cr[o] * L[center + C.loff[o]];
+        } else {
+            const double* __restrict__ cr = coef + C.coef0 + ((cy * C.ncls[1] + cx) * C.ncls[2] + ct) * noff;
+            for (int o = 0; o < noff; ++o) acc += cr[o] * L[center + C.loff[o]];
+        }
+        if (xin) {
+            const int64_t pos = (int64_t)C.node0 + ((int64_t)y * S1 + x) * S2 + t;
+            acc += csr_row_dot(aci, aval, arp[pos], arp[pos + 1], td);
+            gam += L[center] * acc;
+        }
+        qv[k] = acc;
+    }
+    __syncthreads();   // every wave is done reading the p image
+#pragma unroll
+    for (int k = 0; k < CG_MAXI; ++k) {
+        const int it = wid + 4 * k;
+        if (it >= nitems) continue;
+        const int tyl = it / tlen, ti = it - tyl * tlen;
+        L[front + ((tyl + hy) * wx + lane + hx) * tpad + ti + th] = qv[k];
+    }
+    __syncthreads();
+    // 3. coalesced write-back of q over the owned entries (dim 2 fastest)
+    const int sel = tlen == C.tc ? 0 : 1;
+    const int nint = C.ty * CG_TX * tlen;
+    for (int j = threadIdx.x; j < nint; j += BLOCK) {
+        const int r = (int)fdiv((uint32_t)j, C.fd_ic[sel]);
+        const int rem = j - r * (CG_TX * tlen);
+        const int xi = (int)fdiv((uint32_t)rem, C.fd_c[sel]);
+        const int ti = rem - xi * tlen;
+        const int y = y0 + r, xx = x0 + xi;
+        if (y < S0 && xx < S1)
+            q[col0 + ((int64_t)y * S1 + xx) * S2 + t0 + ti] = L[front + ((r + hy) * wx + xi + hx) * tpad + ti + th];
+    }
+    store_partial(gam, part, blockIdx.x);
+}
+
 // x (every CG_XK-th step, CgState::pend), s −= α q, z = M_b⁻¹ s = R_b⁻¹(R_b⁻ᵀ s) per column
 // block, partial Σ sᵀz.  R_b⁻¹ is read as lf_t (bf16 by default, system.hpp; products in fp64):
 // ~13 of the ~61 bytes per column the kernel moves.  The wave's consecutive blocks (one contiguous
@@ -1404,8 +1546,54 @@ bool ns_from_parts(const MfDesc& d, int g, NsTable& T, std::string& why) {
 // The column-mode rows are read from the tile table at t's class (the same sums, bit for bit).
 static inline int offs_of(const NsTable& N, int o, int e) { return N.offs[o][e]; }
 
+// Chunk mode's geometry of a grid whose tile-mode image exceeds LDS: tiles of ty rows × CG_TX dim-1
+// positions × one chunk of dim 2, a chunk being ≤ tc owned nodes with ht halo nodes on either side in
+// a column of odd stride tpad ≥ tc + 2·ht.  Both caps hold: the image (with its pads) within 64 KB and
+// ty·tc ≤ 4·CG_MAXI items.
+//   1. (ty*, tc*) = the pair with the smallest staged-to-owned ratio (ty + 2hy)(tc + 2ht) / (ty·tc)
+//      (the factor wx / CG_TX is common); ties: more items, then the longer chunk (longer runs along
+//      the fastest dimension).  hy = hx = ht = 2: (5, 9), 9·68·13 = 7 956 doubles, ratio 2.76.
+//   2. dim 2 is cut into nch = ceil(S2 / tc*) chunks of near-equal length, chunk k owning
+//      [k·S2/nch, (k + 1)·S2/nch): tc = ceil(S2 / nch) ≤ tc*.
+//   3. ty = the most rows ≤ S0 both caps admit at that tc (the ratio falls with ty): 20 and 28 epochs
+//      run chunks of 7 in an 11-stride image with 6 rows (2.78 instead of (5, 7)'s 3.01).
+// False when no pair fits.
+static bool cg_chunk_geometry(CgGrid& C) {
+    const int S2 = C.shape[2], hy = C.hy, ht = C.ht, cap = 64 * 1024 / (int)sizeof(double);
+    auto pad = [&](int tc) { return (tc + 2 * ht) | 1; };
+    auto fits = [&](int ty, int tc) {
+        return ty * tc <= 4 * CG_MAXI && C.front + (ty + 2 * hy) * C.wx * pad(tc) + ht <= cap;
+    };
+    int by = 0, bc = 0;
+    for (int ty = 1; ty <= 4 * CG_MAXI; ++ty)
+        for (int tc = 1; tc <= std::min(S2, 4 * CG_MAXI / ty); ++tc) {
+            if (!fits(ty, tc)) continue;
+            const int64_t n = (int64_t)(ty + 2 * hy) * (tc + 2 * ht), d = ty * tc;
+            const int64_t bn = (int64_t)(by + 2 * hy) * (bc + 2 * ht), bd = by * bc;
+            if (!by || n * bd < bn * d || (n * bd == bn * d && (d > bd || (d == bd && tc > bc)))) {
+                by = ty;
+                bc = tc;
+            }
+        }
+    if (!by) return false;
+    C.nch = (S2 + bc - 1) / bc;
+    C.tc = (S2 + C.nch - 1) / C.nch;
+    int ty = std::min(by, C.shape[0]);
+    while (ty < C.shape[0] && fits(ty + 1, C.tc)) ++ty;
+    C.ty = ty;
+    C.th = ht;
+    C.tpad = pad(C.tc);
+    C.lds = C.front + (ty + 2 * hy) * C.wx * C.tpad + ht;
+    for (int o = 0; o < C.noff; ++o) C.loff[o] = (C.ooff[o][0] * C.wx + C.ooff[o][1]) * C.tpad + C.ooff[o][2];
+    return true;
+}
+
+// chunks (cg_describe alone passes it, from lsq_set_cg_chunks): a grid of ≤ 4·CG_MAXI nodes along dim
+// 2 whose tile-mode image exceeds 64 KB of LDS is cut along dim 2 too (cg_chunk_geometry) instead of
+// being refused, and the description is chunk mode's (c.chunk; colmode 0: tile mode's step).  Layouts
+// that are column or tile mode without the flag are the same with it.
 bool cg_layout(const std::vector<NsTable>& T, int cus, CgDesc& c, std::vector<double>& coef,
-               std::vector<double>& coefc, std::string& why) {
+               std::vector<double>& coefc, std::string& why, bool chunks = false) {
     c = CgDesc{};
     const int ng = (int)T.size();
     c.n_grids = ng;
@@ -1481,6 +1669,9 @@ bool cg_layout(const std::vector<NsTable>& T, int cus, CgDesc& c, std::vector<do
         if (!T[g].on) continue;
         const int S2 = C.shape[2];
         int back = C.ht;
+        C.tc = S2;
+        C.nch = 1;
+        C.th = 0;
         if (col) {
             C.maxt = S2 == 1 ? 1 : max3;   // register column length: 1, or one length for every 3-D grid
             C.rpw = S2 == 1 ? 4 : 1;
@@ -1491,12 +1682,18 @@ bool cg_layout(const std::vector<NsTable>& T, int cus, CgDesc& c, std::vector<do
         } else {
             C.ty = std::max(1, std::min(C.shape[0], std::min(48 / S2, 4 * CG_MAXI / S2)));
             C.lds = C.front + (C.ty + 2 * C.hy) * C.wx * C.tpad + back;
+            if (chunks && (size_t)C.lds * sizeof(double) > 64 * 1024 && cg_chunk_geometry(C)) c.chunk = 1;
         }
         C.tq = C.tpad;
         if ((size_t)C.lds * sizeof(double) > 64 * 1024) { why = "normal-stencil tile exceeds 64 KB of LDS"; return false; }
         C.nty = (C.shape[0] + C.ty - 1) / C.ty;
         C.ntx = (C.shape[1] + CG_TX - 1) / CG_TX;
-        tiles = col ? std::max(tiles, C.nty * C.ntx) : tiles + C.nty * C.ntx;   // column mode: strip b of every grid
+        // column mode: strip b of every grid; chunk mode: a workgroup per (tile, chunk)
+        tiles = col ? std::max(tiles, C.nty * C.ntx) : tiles + C.nty * C.ntx * C.nch;
+        for (int k = 0; k < 2; ++k) {
+            C.fd_c[k] = make_fastdiv((uint32_t)std::max(C.tc - k, 1));
+            C.fd_ic[k] = make_fastdiv((uint32_t)(CG_TX * std::max(C.tc - k, 1)));
+        }
         ldsmax = std::max(ldsmax, C.lds);
         C.fd_pad = make_fastdiv((uint32_t)C.tpad);
         C.fd_row = make_fastdiv((uint32_t)(C.wx * C.tpad));
@@ -1722,7 +1919,7 @@ bool cg_describe(System& S, std::string& why) {
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, S.device);
     CgDesc c{};
     std::vector<double> coef, coefc;
-    if (!cg_layout(T, cus, c, coef, coefc, why)) return false;
+    if (!cg_layout(T, cus, c, coef, coefc, why, S.cg_chunks && !S.dist)) return false;
     // field-valued parts: 2-D grids, |offsets| ≤ 2, one row scale
     std::vector<CgVar> var;
     int nvb = 0;
@@ -1787,6 +1984,25 @@ bool cg_describe(System& S, std::string& why) {
 // workgroups of the normal-stencil operator of a layout (= its gam partial slots)
 int cg_ns_grid(const CgDesc& c) { return c.rw ? c.rw_nwg : 8 * ((c.ntiles + 7) / 8); }
 int cg_grid_normal(const System& S) { return cg_ns_grid(S.cgh); }
+
+// tile / chunk mode: the entries all workgroups of one normal launch stage from inside their grids
+// (tiles and chunks with their halos, clipped at the grid's faces) — the three dimensions separate
+int64_t cg_chunk_staged(const CgDesc& c) {
+    int64_t all = 0;
+    for (int g = 0; g < c.n_grids; ++g) {
+        const CgGrid& C = c.g[g];
+        if (!C.noff) continue;
+        int64_t ry = 0, rx = 0, rt = 0;
+        for (int i = 0; i < C.nty; ++i)
+            ry += std::min(C.shape[0], (i + 1) * C.ty + C.hy) - std::max(0, i * C.ty - C.hy);
+        for (int i = 0; i < C.ntx; ++i)
+            rx += std::min(C.shape[1], (i + 1) * CG_TX + C.hx) - std::max(0, i * CG_TX - C.hx);
+        for (int k = 0; k < C.nch; ++k)
+            rt += std::min(C.shape[2], (k + 1) * C.shape[2] / C.nch + C.th) - std::max(0, k * C.shape[2] / C.nch - C.th);
+        all += ry * rx * rt;
+    }
+    return all;
+}
 
 // q = N_s p, p = z + β p_old (β from betap, else the CG state's) written to pnew (when non-null),
 // gam partials pᵀN_s p to part[0, cg_ns_grid(ch)): the wave-strip kernel where the layout allows,
@@ -2101,8 +2317,9 @@ void cg_launch_normal(System& S, const CgGrids& g, const double* pold, double* p
             cg_launch_xedge(S, g, pnew, S.stream);
             cg_launch_var(S, pnew, S.cg_q.p, S.cg_part_g.p + g.gN + S.cgh.nedge, S.stream, S.cst.p);
         }
-    } else {
-        hipLaunchKernelGGL(k_cg_normal, dim3(g.gN), dim3(BLOCK), lds, S.stream, S.cst.p, S.cgd.p, S.cg_coef.p, S.cg_z.p,
+    } else {   // tile mode, or its tiles cut along dim 2 too (chunk mode): the same arguments, step and partial slots
+        hipLaunchKernelGGL(S.cgh.chunk ? k_cg_normal_chunk : k_cg_normal, dim3(g.gN), dim3(BLOCK), lds, S.stream, S.cst.p,
+                           S.cgd.p, S.cg_coef.p, S.cg_z.p,
                            pold, pnew, S.cg_q.p, S.ATd.rp.p, S.ATd.ci.p, S.ATd.val.p, S.cg_t.p, S.cg_part_g.p);
         cg_launch_var(S, pnew, S.cg_q.p, S.cg_part_g.p + g.gN, S.stream, S.cst.p);
     }
@@ -2382,6 +2599,9 @@ void cg_kernel_bytes(const System& S, int precond, double out[3]) {
     } else {
         out[0] = 12.0 * zd + 16.0 * nd + 8.0 * md;
         out[1] = 32.0 * nf + 12.0 * zd + 4.0 * ne + 8.0 * md;
+        // chunk mode: z and p_old over every staged image inside its grid (the halos of dim 2 are no
+        // longer a tile's own columns), p and q over the owned entries
+        if (S.cgh.chunk) out[1] += 16.0 * ((double)cg_chunk_staged(S.cgh) - nf);
     }
     if (xr_active(S)) out[0] += xr_step_bytes(S);
     for (const CgVar& V : S.cg_var)   // field-valued parts: fields + p once, q read and written
@@ -2420,6 +2640,42 @@ void sgrid_values(System& S, const double* dbp);
 bool cg_available(System& S, int precond) {
     if (precond != 1 && precond != 3 && precond != 4) return false;
     return cg_prepare(S, precond) && (precond != 4 || S.mg);
+}
+
+// lsq_set_cg_chunks: the flag cg_describe hands to cg_layout.  A change drops what was built for the
+// other layout, as a change of the part row scales does: the description, the captured iterations and
+// the multigrid levels; the next cg_prepare lays out afresh.
+void cg_set_chunks(System& S, bool on) {
+    if (S.cg_chunks == on) return;
+    S.cg_chunks = on;
+    graph_cache_drop(&S);
+    mg_free(S.mg);
+    S.mg = nullptr;
+    S.mg_why.clear();
+    S.cg_ok = false;
+    S.cg_why.clear();
+    S.cg_ready = false;
+}
+
+// lsq_cg_layout_info: {mode (0 none, 1 column, 2 tile, 3 chunk), ty, tc, chunks of the grid with the
+// longest dim 2, its LDS column stride, LDS bytes of the largest tile, workgroups of one normal launch, 0}
+void cg_layout_info(System& S, int64_t* out8) {
+    std::fill(out8, out8 + 8, (int64_t)0);
+    // the geometry does not depend on the row scales: a description that stands is read as it is
+    if (!(S.cg_ok && S.cgd.p) && !cg_prepare(S, 1)) return;
+    const CgDesc& c = S.cgh;
+    const CgGrid* G = nullptr;
+    for (int g = 0; g < c.n_grids; ++g)
+        if (c.g[g].noff && (!G || c.g[g].shape[2] > G->shape[2])) G = &c.g[g];
+    out8[0] = c.colmode ? 1 : c.chunk ? 3 : 2;
+    if (G) {
+        out8[1] = G->ty;
+        out8[2] = G->tc;
+        out8[3] = G->nch;
+        out8[4] = G->tpad;
+    }
+    out8[5] = (int64_t)c.lds_max * (int64_t)sizeof(double);
+    out8[6] = cg_ns_grid(c);
 }
 
 int cg_solve(System& S, const double* h_b, double* h_x, const lsq_opts& o, lsq_stats* stats) {
@@ -2557,8 +2813,9 @@ static void cg_profile_steps(System& S, int reps, int precond, unsigned mask, do
 void cg_profile(System& S, int reps, int precond, double* out) {
     const CgGrids g = cg_grids(S, precond);
     // bit 0: data rows matrix-free (else stored Ad / ATd); bit 1: wave-strip normal operator; bit 2:
-    // column mode (else tile mode)
-    out[7] = (cg_use_dmf(S) ? 1.0 : 0.0) + (S.cgh.rw ? 2.0 : 0.0) + (S.cgh.colmode ? 4.0 : 0.0);
+    // column mode (else tile mode); bit 3: chunk mode (tile mode's step on tiles cut along dim 2; bit 2 clear)
+    out[7] = (cg_use_dmf(S) ? 1.0 : 0.0) + (S.cgh.rw ? 2.0 : 0.0) + (S.cgh.colmode ? 4.0 : 0.0) +
+             (S.cgh.chunk ? 8.0 : 0.0);
     cg_kernel_bytes(S, precond, out + 4);
     if (cg_live(S, precond)) {
         const int rows = S.cgh.colmode ? CG_ATQ : CG_AD;   // the last stage of the data rows' share

@@ -225,6 +225,12 @@ struct CgGrid {
     // wave-strip operator (lsqr_cg_rw.inc): strips of rw_sx dim-1 positions × rw_ry rows, rw_nsx ×
     // rw_nry of them, rw_chunk per XCD; its class table (per dim-0 class) from coefc[rwc0]
     int32_t rw_sx, rw_nsx, rw_ry, rw_nry, rw_chunk, rwc0;
+    // chunk mode (k_cg_normal_chunk): a tile is ty rows × CG_TX dim-1 positions × one of nch chunks of
+    // dim 2, chunk k owning t in [k·S2/nch, (k+1)·S2/nch) (tc or tc − 1 nodes) and staging th more on
+    // either side; tpad is then the chunk image's stride (odd, ≥ tc + 2·th).  A grid that fits tile
+    // mode keeps its geometry as one chunk: nch = 1, tc = S2, th = 0
+    int32_t tc, nch, th, cpad;
+    FastDiv fd_c[2], fd_ic[2];               // ÷ tlen, ÷ (CG_TX · tlen) for tlen = tc, tc − 1: interior index
 };
 struct BlkAffine {
     int64_t base[16], stride[16];
@@ -270,6 +276,7 @@ struct CgDesc {
     int32_t w8, rw_kt;                       // column mode: the CG iteration runs k_cg_normal_col8 (8-wave workgroups);
                                              // the wave-strip table's dim-2 class width (rw_nc; −1 one row per t)
     int32_t rw, rw_nwg;                      // the wave-strip operator k_cg_normal_rw applies; its workgroups
+    int32_t chunk, cpad;                     // chunk mode: tile mode whose tiles are also cut along dim 2 (colmode = 0)
     CgGrid g[MF_MAX_GRIDS];
 };
 // CGNR data rows without a stored matrix (lsqr_cg.inc, k_cg_dmf_*): when every interpolation
@@ -602,6 +609,7 @@ struct System {
     // CGNR (method 1): normal-stencil description + coefficient table, rebuilt when the part
     // row scales change; vectors in the full column space
     bool cg_ok = false;            // the structured normal operator exists for this system
+    bool cg_chunks = false;        // lsq_set_cg_chunks: chunk mode where a tile-mode image exceeds LDS
     int64_t cg_data_cols = 0;      // columns touched by the data rows
     DmfDesc dmf{};                  // matrix-free data rows for CGNR (ok = 0: use Ad / ATd)
     DBuf<double> dmf_pt;            // per sorted point: f_y, f_x, f_t, row scale (double4)

@@ -86,7 +86,10 @@ DEFAULTS = {'reference_epoch': 0, 'W_ctr': 1e4, 'return_fit_objects': False, 'ma
             'lsq_E_border_solve': False,
             # sensor bias grids beside bias_params / data_slope_sensors eliminated jointly (opt-in; the
             # bias IDs and slope groups must nest in the grids' sensors, as with 'sensor' in bias_params)
-            'lsq_sgrid_joint': False}
+            'lsq_sgrid_joint': False,
+            # CGNR on dz grids of 20 to 64 epochs: the normal operator's tiles cut along time too (chunk
+            # mode) instead of method 1 falling back to LSQR (opt-in; below 20 epochs the key does nothing)
+            'lsq_cg_chunks': False}
 
 OUT_OF_SCOPE = ('lagrangian_coords', 'constraint_scaling_maps', 'mask_file', 'bias_edit_vals')
 
@@ -96,8 +99,13 @@ class FitSystem:
     Ip_c as a column map; rows re-weighted / re-selected per outer iteration."""
 
     def __init__(self, G_data, Gc, keep_cols, n_full, device=0, structured=True, grids=None, bias=None,
-                 extra_ops=None, extra_csr=None, extra_mg=False, sensor_grids=None, joint=False, iterative=True):
-        """sensor_grids: the dict of setup_sensor_grid_bias.sensor_grid_device_form — eliminated sensor
+                 extra_ops=None, extra_csr=None, extra_mg=False, sensor_grids=None, joint=False, iterative=True,
+                 cg_chunks=False):
+        """cg_chunks: CGNR's chunk mode (LSQSolver.set_cg_chunks), set before the formation: a dz grid of
+        20 to 64 epochs then runs method 1 as CGNR instead of falling back to LSQR.  What tile mode
+        refuses stays refused: no multigrid, no eliminated bias / sensor_grids (this constructor raises),
+        extra rows take the COO path.
+        sensor_grids: the dict of setup_sensor_grid_bias.sensor_grid_device_form — eliminated sensor
         bias grids (LSQSolver.set_sensor_grids), together with bias only when joint=True
         (lsq_set_sensor_grids_joint: every bias ID and slope group inside one grid's rows or outside
         every grid; expand() then lays the columns out as the reference does: the biases, the slopes,
@@ -133,6 +141,9 @@ class FitSystem:
         self.keep_cols = keep_cols
         self.n_full = int(n_full)
         self.solver = LSQSolver(device)
+        self.cg_chunks = bool(cg_chunks)
+        if self.cg_chunks:
+            self.solver.set_cg_chunks(True)
         self.solver.set_col_map(self.n_full, keep_cols)
         m = self.n_data + self.n_con
         extra_ops = list(extra_ops or [])
@@ -187,6 +198,8 @@ class FitSystem:
                               RuntimeWarning, stacklevel=2)
                 self.solver.close()   # a fresh handle: nothing staged, nothing half formed
                 self.solver = LSQSolver(device)
+                if self.cg_chunks:
+                    self.solver.set_cg_chunks(True)
                 self.solver.set_col_map(self.n_full, keep_cols)
                 desc = None
         self.desc = desc           # the descriptors (bench.py's structured CPU baseline reads them)
@@ -512,6 +525,9 @@ def iterate_fit(data, system, rhs, TCinv, G_data, Gc, in_TSE, timing, args, grid
         system.stats['precond'] = opts['precond']
         # did this solve run the multigrid with the priors' rows lumped into it (lsq_prior_mg)?
         timing['prior_mg'] = bool(opts['precond'] == 4 and getattr(system, 'n_extra', 0) > 0)
+        # did this solve run CGNR in chunk mode (lsq_cg_chunks on a dz grid of 20 to 64 epochs)?
+        timing['cg_chunks'] = bool(getattr(system, 'cg_chunks', False) and system.stats['method'] == 1 and
+                                   system.solver.cg_layout_info()['mode'] == 'chunk')
         prev_solve = (weight, np.asarray(in_TSE, bool).copy() if opts['precond'] == 4 else None)
         system.last_x = x   # compact solution: z_est and the constraint statistics read it, not m0
         timing['sparseqr_solve'] = time() - tic
@@ -773,14 +789,14 @@ def _bias_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, bias_model, m
             bias += ((group, u, np.full((len(slope_dict), 2), 1. / (bias_model['E_slope_bias'] * SLOPE_RESCALE))),)
         try:
             return FitSystem(G_grid, Gc_grid, keep_cols[keep_cols < n_grid], n_grid, device=device, grids=grids,
-                             bias=bias, sensor_grids=sg, joint=sg is not None)
+                             bias=bias, sensor_grids=sg, joint=sg is not None, cg_chunks=args['lsq_cg_chunks'])
         except NativeError as e:
             if mode == 'eliminate':
                 raise
             if sg is not None:
                 warnings.warn(f"smooth_fit: lsq_bias='auto' with lsq_sgrid_joint takes 'columns': the device refuses "
                               f"the joint elimination ({e})", RuntimeWarning, stacklevel=3)
-    return FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=device, grids=grids)
+    return FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=device, grids=grids, cg_chunks=args['lsq_cg_chunks'])
 
 
 def _sgrid_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, sgrid_sensor, constraint_op_list, mode, grids,
@@ -801,11 +817,11 @@ def _sgrid_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, sgrid_sensor
         sg = sensor_grid_device_form(data, grids, sgrid_sensor, constraint_op_list)
         try:
             return FitSystem(G_grid, Gc_grid, keep_cols[keep_cols < n_grid], n_grid, device=device, grids=grids,
-                             sensor_grids=sg)
+                             sensor_grids=sg, cg_chunks=args['lsq_cg_chunks'])
         except NativeError:
             if mode == 'eliminate':
                 raise
-    return FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=device, grids=grids)
+    return FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=device, grids=grids, cg_chunks=args['lsq_cg_chunks'])
 
 
 def smooth_fit(**kwargs):
@@ -836,6 +852,8 @@ def smooth_fit(**kwargs):
         raise ValueError(f"smooth_fit: lsq_E_border_solve must be True or False, not {args['lsq_E_border_solve']!r}")
     if not isinstance(args['lsq_sgrid_joint'], (bool, np.bool_)):
         raise ValueError(f"smooth_fit: lsq_sgrid_joint must be True or False, not {args['lsq_sgrid_joint']!r}")
+    if not isinstance(args['lsq_cg_chunks'], (bool, np.bool_)):
+        raise ValueError(f"smooth_fit: lsq_cg_chunks must be True or False, not {args['lsq_cg_chunks']!r}")
     bias_mode = args['lsq_bias']
     if args['bias_params'] is not None:
         if bias_mode is None:
@@ -1082,7 +1100,7 @@ def smooth_fit(**kwargs):
                                                           keep_cols.size <= args['lsq_dense_max'])
                 system = FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=devices[0], grids=grids,
                                    extra_ops=prior_ops, extra_mg=bool(args['lsq_prior_mg']) and bool(prior_ops),
-                                   iterative=not dense)
+                                   iterative=not dense, cg_chunks=args['lsq_cg_chunks'])
             if b_rows_all is not None and not getattr(system, 'n_extra', 0):
                 b_rows = max(b_rows, b_rows_all)
             if b_rows_sg is not None and getattr(system, 'sg', None) is None:

@@ -248,7 +248,26 @@ class LSQSolver:
         d['bytes'] = {'cg_data': float(o[4]), 'cg_normal': float(o[5]), 'cg_update': float(o[6])}
         d['data_rows'] = 'matrix-free' if int(o[7]) & 1 else 'stored'
         d['normal_kernel'] = 'wave-strip' if int(o[7]) & 2 else 'ring'
-        d['normal_mode'] = 'column' if int(o[7]) & 4 else 'tile'
+        d['normal_mode'] = 'column' if int(o[7]) & 4 else 'chunk' if int(o[7]) & 8 else 'tile'
+        return d
+
+    def set_cg_chunks(self, on=True):
+        """Chunk mode for CGNR (lsq_set_cg_chunks): grids of 20 to 64 nodes along their last dimension,
+        whose tile-mode image exceeds LDS, get tiles that are also cut along that dimension instead of
+        the refusal that sends method 1 to LSQR.  Column- and tile-mode systems are unchanged.  A change
+        drops the CGNR description, the captured iterations and the multigrid levels."""
+        self._check(self._L.lsq_set_cg_chunks(self._h, 1 if on else 0), 'lsq_set_cg_chunks')
+
+    def cg_layout_info(self):
+        """The normal operator's layout (lsq_cg_layout_info; builds the description if needed): mode
+        ('none' with its reason, 'column', 'tile' or 'chunk'), and of the grid with the longest last
+        dimension the rows per tile ty, the chunk length tc, the chunks per tile and the LDS stride of a
+        node column tcpad; the LDS bytes of the largest tile and the workgroups of one normal launch."""
+        o = np.zeros(8, np.int64)
+        self._check(self._L.lsq_cg_layout_info(self._h, ptr(o)), 'lsq_cg_layout_info')
+        d = dict(zip(['ty', 'tc', 'chunks', 'tcpad', 'lds_bytes', 'workgroups'], (int(v) for v in o[1:7])))
+        d['mode'] = ('none', 'column', 'tile', 'chunk')[int(o[0])]
+        d['reason'] = '' if o[0] else self._L.lsq_last_error(self._h).decode()
         return d
 
     def mg_info(self):
