@@ -555,7 +555,10 @@ int lsq_cg_layout_info(lsq_handle* h, int64_t* out8);
  * (S0, S1, n_full, removed epoch) — cap must hold 1 + 4L values.  lsq_mg_apply on level l's full
  * column space (z0 grid then dz grid, in the system's order): what 0: y = N_l x (level 0: AᵀA;
  * coarse levels: Galerkin PᵀNP of the stencil rows + the (y, x)-lumped data rows), 1: y = the
- * V-cycle applied to x (level 0), 2: y[0] = the smoother's λ_max(M⁻¹N) estimate of level l.
+ * V-cycle from level l down applied to x (the coarsest level: its dense inverse; a system with z0
+ * on a refined lattice exposes level 0 only), 2: y[0] = the smoother's λ_max(M⁻¹N) estimate of level l,
+ * 3: y[0] = the kernel family of level l's operator (0 ring kernel + x-edge pass, 1 k_mg_direct,
+ * 2 k_mg_tile, 3 k_mg_tile_kt, −1 the coarsest level; systems with z0 on the dz lattice).
  * Both build the hierarchy for the current row weights / mask. */
 int lsq_mg_info(lsq_handle* h, int64_t* out, int64_t cap);
 int lsq_mg_apply(lsq_handle* h, int32_t level, int32_t what, const double* x, double* y);

@@ -574,7 +574,7 @@ int lsq_mg_info(lsq_handle* h, int64_t* out, int64_t cap) {
 int lsq_mg_apply(lsq_handle* h, int32_t level, int32_t what, const double* x, double* y) {
     return guarded(h, [&](lsq::System& S) {
         if (!S.G.rp.p) return fail(S, "lsq_mg_apply: no matrix");
-        if (!y || (what != 2 && !x)) return fail(S, "lsq_mg_apply: null vector");
+        if (!y || (what != 2 && what != 3 && !x)) return fail(S, "lsq_mg_apply: null vector");
         lsq::mg_test_apply(S, level, what, x, y);
         return 0;
     });

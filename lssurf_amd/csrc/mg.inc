@@ -160,7 +160,13 @@ namespace {
 // 3/1 42 / 0.177 s, 3/2 41 / 0.206 s — degree 1 halves the coarse levels' latency-bound launches
 // for two more iterations.
 constexpr int MG_DEG0 = 2, MG_DEG = 1;
-constexpr int MG_POW = 10;       // power steps per level for λ_max(M⁻¹N)
+// Power steps per level for λ_max(M⁻¹N).  A Chebyshev smoother on [0.11 λ, 1.1 λ] contracts only
+// below 2θ = 1.21 λ, so the estimate must reach λ_max / 1.21.  λ_max / λ after 10, 16, 20 steps (host
+// Lanczos against the device's λ, tests/test_gpu_mg_vcycle.py): t256 level 2 1.42, 1.17, 1.12; t64 with
+// edited rows level 0 1.24, 1.13, 1.05; a 5 × 200 lattice level 0 1.23, 1.20, 1.18 (the worst at 20).
+// 10 → 20: C4 set-up 11.5 → 18.0 ms per solve (solve 117 ms, 47 iterations either way), t64 52 → 53
+// and t256 55 → 56 iterations (the wider interval).
+constexpr int MG_POW = 20;
 constexpr int MG_COARSE = 5;     // coarsest level: at most this many nodes per side
 // … or at most this many columns (LSQ_MG_COARSE_COLS; round 6): an elongated lattice — a rank's
 // y-slab window, the notebooks' x-t strips — reaches ≤ 5 rows long before ≤ 5 columns, and each
@@ -2951,7 +2957,10 @@ int mg_info(System& S, int64_t* out, int64_t cap) {
 }
 
 // what 0: y = N_ℓ x over level ℓ's full column space (ℓ ≥ 1: Galerkin stencil + lumped data;
-// removed columns: 0); 1: y = V(x) on level 0; 2: y[0] = λ estimate of level ℓ
+// removed columns: 0); 1: y = V_ℓ(x), the cycle from level ℓ down (the coarsest level: its dense
+// inverse; z0-refined systems: ℓ = 0 only); 2: y[0] = λ estimate of level ℓ; 3: y[0] = the kernel
+// family of level ℓ's operator (0 ring + x-edge pass, 1 k_mg_direct, 2 k_mg_tile, 3 k_mg_tile_kt;
+// −1: the coarsest level, no operator kernel)
 void mg_test_apply(System& S, int level, int what, const double* hx, double* hy) {
     if (!cg_prepare(S, 4) || !S.mg) throw std::invalid_argument("multigrid unavailable: " + (S.cg_ok ? S.mg_why : S.cg_why));
     MgHier& H = *S.mg;
@@ -2981,6 +2990,11 @@ void mg_test_apply(System& S, int level, int what, const double* hx, double* hy)
         return;
     }
     if (level < 0 || level >= (int)H.lev.size()) throw std::invalid_argument("lsq_mg_apply: level out of range");
+    if (what == 3) {   // fixed at the hierarchy's build: no set-up needed
+        const MgLevel& Vl = H.lev[level];
+        hy[0] = Vl.coarsest ? -1.0 : Vl.tile ? (Vl.tile_kt ? 3.0 : 2.0) : Vl.direct ? 1.0 : 0.0;
+        return;
+    }
     cg_workspace(S);
     cg_dmf_prepare(S);
     mg_setup(S);
@@ -3005,13 +3019,19 @@ void mg_test_apply(System& S, int level, int what, const double* hx, double* hy)
         HIP_CHECK(hipStreamSynchronize(st));
         for (int64_t i = 0; i < nf; ++i) hy[i] = -tmp[i];
     } else if (what == 1) {
-        if (level != 0) throw std::invalid_argument("lsq_mg_apply: the V-cycle starts on level 0");
-        S.cg_s.upload(hx, nf, st);
-        S.cg_z.zero(st);
-        mg_vcycle(S, H, 0, ms);
-        S.cg_z.download(hy, nf, st);
+        if (level == 0) {
+            S.cg_s.upload(hx, nf, st);
+            S.cg_z.zero(st);
+            mg_vcycle(S, H, 0, ms);
+            S.cg_z.download(hy, nf, st);
+        } else {   // the cycle from a coarse level (the coarsest: its dense inverse), on that level's own vectors
+            V.r.upload(hx, nf, st);
+            V.x.zero(st);
+            mg_vcycle(S, H, level, ms);
+            V.x.download(hy, nf, st);
+        }
     } else {
-        throw std::invalid_argument("lsq_mg_apply: what must be 0, 1 or 2");
+        throw std::invalid_argument("lsq_mg_apply: what must be 0, 1, 2 or 3");
     }
     KERNEL_CHECK();
     HIP_CHECK(hipStreamSynchronize(st));

@@ -278,13 +278,15 @@ class LSQSolver:
         return [tuple(int(v) for v in o[1 + 4 * l:4 + 4 * l]) for l in range(L)], int(o[4])
 
     def mg_apply(self, level, what, x=None):
-        """Multigrid test hook: what 0 → N_l x on level l's full column space; 1 → V-cycle(x)
-        (level 0); 2 → the smoother's λ_max(M⁻¹N) estimate of level l."""
+        """Multigrid test hook: what 0 → N_l x on level l's full column space; 1 → the V-cycle from
+        level l down applied to x (the coarsest level: its dense inverse; z0-refined systems: level 0
+        only); 2 → the smoother's λ_max(M⁻¹N) estimate of level l; 3 → the kernel family of level l's
+        operator (0 ring, 1 direct, 2 tile, 3 class-compressed tile, −1 the coarsest level)."""
         levels, _ = self.mg_info()
         nf = levels[level][2]
-        if what == 2:
+        if what in (2, 3):
             y = np.zeros(1)
-            self._check(self._L.lsq_mg_apply(self._h, int(level), 2, None, ptr(y)), 'lsq_mg_apply')
+            self._check(self._L.lsq_mg_apply(self._h, int(level), int(what), None, ptr(y)), 'lsq_mg_apply')
             return float(y[0])
         xx = as_c(x, np.float64)
         if xx.size != nf:

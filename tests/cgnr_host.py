@@ -47,7 +47,11 @@ MIN_PIVOT = 1e-8   # k_block_factor calls a column dead at d ≤ 1e-12·d0: no i
 def block_factors(A, blocks, round=True):
     """[(C, R̃)] per block size: R̃ (n_blocks, k, k) the upper R_b⁻¹ of N_b = (AᵀA)_bb = R_bᵀR_b,
     rounded to bf16 when `round`."""
-    N = (A.T @ A).tocsr()
+    return normal_factors((A.T @ A).tocsr(), blocks, round)
+
+
+def normal_factors(N, blocks, round=True):
+    """block_factors of a normal matrix N given as such (tests/mg_host.py: a multigrid level's)."""
     out = []
     for C in blocks:
         nb, k = C.shape
