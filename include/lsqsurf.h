@@ -550,6 +550,20 @@ int lsq_profile_cg(lsq_handle* h, int32_t reps, int32_t precond, double* out8);
  * longest last dimension, its chunk length tc, its chunks per tile, the LDS stride of its node
  * columns, LDS bytes of the largest tile, workgroups of one normal-operator launch, 0}. */
 int lsq_set_cg_chunks(lsq_handle* h, int32_t on);
+/* Tile and chunk mode on matrix-free data rows.  lsq_set_cg_tile_dmf(h, 1), called BEFORE the
+ * formation (lsq_set_matrix_stencil), lets the formation keep the sorted point table for a 3-D
+ * interpolation grid of up to 64 nodes along its last dimension (16 without it), and lets a tile- or
+ * chunk-mode CGNR step (16 to 19 nodes; 20 to 64 with lsq_set_cg_chunks) run in column mode's order:
+ * q = N_s p by k_cg_normal / k_cg_normal_chunk without the stored ATd rows, t = Ad·p from the points,
+ * the elimination of data biases, slopes and sensor grids, then the node gather (k_cg_dmf_atq, or
+ * k_cg_dmf_atq_long above 16 nodes).  lsq_set_data_bias, lsq_set_data_slope and lsq_set_sensor_grids
+ * then run on such a handle; lsq_profile_cg reports mode bit 1 beside a clear bit 4.  Still refused
+ * there: multigrid (precond 4), extra rows, more than 64 nodes, 20 or more without
+ * lsq_set_cg_chunks.  Column-mode systems, and every system without the switch, run exactly as
+ * before.  A change drops the CGNR description, the captured iterations and the multigrid levels.
+ * Returns −2 (reason in lsq_last_error) on a rank of a distributed, virtual or device group.
+ * Default: off. */
+int lsq_set_cg_tile_dmf(lsq_handle* h, int32_t on);
 int lsq_cg_layout_info(lsq_handle* h, int64_t* out8);
 /* Multigrid (precond 4) test hooks.  lsq_mg_info: out[0] = levels L, then per level
  * (S0, S1, n_full, removed epoch) — cap must hold 1 + 4L values.  lsq_mg_apply on level l's full

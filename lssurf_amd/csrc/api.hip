@@ -15,6 +15,7 @@ int cg_solve(System& S, const double* h_b, double* h_x, const lsq_opts& o, lsq_s
 int cg_iterate(System& S, const double* h_b, int64_t iters, const lsq_opts& o, lsq_stats* stats);
 void cg_profile(System& S, int reps, int precond, double* out);
 void cg_set_chunks(System& S, bool on);
+void cg_set_tile_dmf(System& S, bool on);
 void cg_layout_info(System& S, int64_t* out8);
 void cg_profile_xr(System& S, int reps, int precond, double* out);
 void cg_apply_normal(System& S, const double* h_p, double* h_q);
@@ -539,6 +540,16 @@ int lsq_set_cg_chunks(lsq_handle* h, int32_t on) {
             return fail(S, "lsq_set_cg_chunks: chunk mode is single-GPU; a rank of a distributed, virtual or device "
                            "group runs the column-mode operator");
         lsq::cg_set_chunks(S, on != 0);
+        return 0;
+    });
+}
+
+int lsq_set_cg_tile_dmf(lsq_handle* h, int32_t on) {
+    return guarded(h, [&](lsq::System& S) {
+        if (S.dist || S.virt || S.comm || S.nranks > 1)
+            return fail(S, "lsq_set_cg_tile_dmf: tile and chunk mode are single-GPU; a rank of a distributed, virtual or "
+                           "device group runs the column-mode operator");
+        lsq::cg_set_tile_dmf(S, on != 0);
         return 0;
     });
 }

@@ -701,7 +701,8 @@ void build_dmf_mixed(System& S, const lsq_grid_desc& gz, const lsq_grid_desc& g3
 }
 
 // Matrix-free CGNR data rows (DmfDesc): eligible when every interpolation grid is 2-D or 3-D on one
-// shared (y, x) lattice (≤ 2 2-D parts, ≤ 1 3-D part with ≤ CG_MAXT t nodes).  The float
+// shared (y, x) lattice (≤ 2 2-D parts, ≤ 1 3-D part with ≤ CG_MAXT t nodes; ≤ DMF_MAXT_LONG under
+// lsq_set_cg_tile_dmf, set before the formation, on the shared lattice alone).  The float
 // subscripts are computed here exactly as k_gen_rows computes them (one IEEE division each), the
 // points counting-sorted by (y, x) cell (stable: data-row order within a cell).
 void build_dmf(System& S, int32_t n_grids, const lsq_grid_desc* grids, int32_t n_interp, const int32_t* interp_grid,
@@ -725,14 +726,14 @@ void build_dmf(System& S, int32_t n_grids, const lsq_grid_desc* grids, int32_t n
             if (D.n2 == 2) return;
             D.col2[D.n2++] = g.col0;
         } else {
-            if (D.n3 == 1 || g.shape[2] < 2 || g.shape[2] > CG_MAXT) return;
+            if (D.n3 == 1 || g.shape[2] < 2 || g.shape[2] > (S.cg_tile_dmf ? DMF_MAXT_LONG : CG_MAXT)) return;
             D.col3 = g.col0;
             D.n3 = 1;
             g3 = &g;
         }
     }
     if (!shared) {   // z0 on a 2× refinement of the dz lattice: the multigrid's coarse data rows
-        if (n_interp != 2 || D.n2 != 1 || D.n3 != 1) return;
+        if (n_interp != 2 || D.n2 != 1 || D.n3 != 1 || g3->shape[2] > CG_MAXT) return;
         const lsq_grid_desc& gz = grids[interp_grid[0]].ndim == 2 ? grids[interp_grid[0]] : grids[interp_grid[1]];
         for (int d = 0; d < 2; ++d)
             if (gz.shape[d] != 2 * g3->shape[d] - 1 || gz.b0[d] != g3->b0[d] || 2.0 * gz.delta[d] != g3->delta[d]) return;

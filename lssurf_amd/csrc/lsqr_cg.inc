@@ -16,6 +16,8 @@
 //   k_cg_data    t = Ad·p,  p = z + β p_old gathered on the fly           (data rows)
 //   k_cg_normal  p = z + β p_old staged per tile in LDS (written once), q = N p + ATd·t, Σ p·q
 //                (k_cg_normal_chunk where a tile of whole dim-2 columns exceeds LDS: lsq_set_cg_chunks)
+//                (lsq_set_cg_tile_dmf: the <false> instantiations, q = N_s p alone, then column mode's
+//                matrix-free k_cg_dmf_ad, the eliminations and k_cg_dmf_atq / k_cg_dmf_atq_long)
 //   k_cg_alpha   α = ρ / pᵀq; Lanczos-derived ‖A‖ and ‖Δx‖ estimates               (1 block)
 //   k_cg_block   x += α p, s −= α q, z = M⁻¹ s (block-Jacobi R_b⁻¹R_b⁻ᵀ, or Jacobi), Σ sᵀz
 //   k_cg_beta    β = ρ'/ρ, ‖r‖² −= α ρ, LSQR stopping rules                         (1 block)
@@ -379,6 +381,111 @@ __global__ __launch_bounds__(BLOCK) void k_cg_dmf_atq(const CgState* st, DmfDesc
                 const int nl = e / S2;
                 qc[e] = qv[k] + L[(e - nl * S2) * 64 + nl];
             }
+        }
+    }
+}
+
+// dmf_node_gather for one chunk [t0, t0 + tlen) of the node's column: every point of the node is
+// walked in the same sorted order and adds the corners of its t cell that fall inside the chunk to
+// acc[(t − t0)·64], so each entry of the column receives the terms, and the order, it has there.
+__device__ __forceinline__ double dmf_node_gather_chunk(const DmfDesc& D, const int32_t* __restrict__ cell,
+                                                        const double4* __restrict__ pt, const double* __restrict__ td,
+                                                        int iy, int ix, int t0, int tlen, double* __restrict__ acc) {
+    const int C1 = D.S1 - 1;
+    double a2 = 0.0;
+    const bool r0 = iy >= 1, r1 = iy <= D.S0 - 2;
+    const int ra = r0 ? (iy - 1) * C1 : 0, rb = r1 ? iy * C1 : 0;
+    const int cxl = max(ix - 1, 0), cxh = min(ix, C1 - 1);
+    const int a0 = r0 ? cell[ra + cxl] : 0, a1 = r0 ? cell[ra + cxh + 1] : 0;
+    const int b0 = r1 ? cell[rb + cxl] : 0, b1 = r1 ? cell[rb + cxh + 1] : 0;
+    const int na = a1 - a0, ntot = na + (b1 - b0);
+    for (int j0 = 0; j0 < ntot; j0 += DMF_U) {
+        double4 P[DMF_U];
+        double tj[DMF_U];
+#pragma unroll
+        for (int u = 0; u < DMF_U; ++u) {
+            const int j = j0 + u;
+            const int idx = j < na ? a0 + j : b0 + (j - na);
+            const bool in = j < ntot;
+            P[u] = in ? pt[idx] : make_double4(0.0, 0.0, 0.0, 0.0);
+            tj[u] = in ? td[idx] : 0.0;   // past the node's points: 0·w
+        }
+#pragma unroll
+        for (int u = 0; u < DMF_U; ++u) {
+            double fy, fx, ft;
+            const int pcy = dmf_cell(P[u].x, D.S0, fy), pcx = dmf_cell(P[u].y, D.S1, fx);
+            const double wt = (pcy == iy ? 1.0 - fy : fy) * (pcx == ix ? 1.0 - fx : fx);
+            a2 += wt * tj[u];
+            const int tl = dmf_cell(P[u].z, D.S2, ft) - t0;   // the cell's lower corner, chunk-relative
+            if (tl >= 0 && tl < tlen) acc[tl * 64] += (wt * (1.0 - ft)) * tj[u];
+            if (tl >= -1 && tl + 1 < tlen) acc[(tl + 1) * 64] += (wt * ft) * tj[u];
+        }
+    }
+    return a2;
+}
+
+// k_cg_dmf_atq for a 3-D part of CG_MAXT < S2 ≤ DMF_MAXT_LONG t nodes (lsq_set_cg_tile_dmf).  A whole
+// column per lane no longer fits LA (64 t × 64 lanes × 8 B = 32 KB a wave), so the column is cut into
+// nch = ⌈S2 / DMF_TC⌉ chunks of near-equal length ≤ DMF_TC and a wave takes one (strip, chunk): it
+// walks all the points of its lanes' nodes and keeps the corners that fall in its chunk
+// (dmf_node_gather_chunk).  The chunks of a strip sit in consecutive waves (of one workgroup when
+// nch = 4 or 2), so the points' second to fourth reads hit the vector L1; LDS stays 32 KB a
+// workgroup and the occupancy that of k_cg_dmf_atq<CG_MAXT> (DESIGN.md §3).  Chunk 0's wave also
+// adds the 2-D parts' sum.  Same sums in the same order as one wave per whole column would give.
+__global__ __launch_bounds__(BLOCK) void k_cg_dmf_atq_long(const CgState* st, DmfDesc D,
+                                                           const int32_t* __restrict__ cell,
+                                                           const double4* __restrict__ pt,
+                                                           const double* __restrict__ td, double* __restrict__ q,
+                                                           CgState* ast, const double* apg, int ang, const double* apt,
+                                                           int ant) {
+    const int stopped = st->stop;   // as k_cg_dmf_atq: read once, before workgroup 0's α body may set it
+    if (ast && blockIdx.x == 0) cg_alpha_body(ast, apg, ang, apt, ant, nullptr);
+    if (stopped) return;
+    __shared__ double LA[BLOCK / 64][DMF_TC * 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int S2 = D.S2, nsx = (D.S1 + 63) / 64, nch = (S2 + DMF_TC - 1) / DMF_TC;
+    const int64_t unit = (int64_t)xcd_block(blockIdx.x, gridDim.x) * (BLOCK / 64) + w;   // grid: a multiple of 8
+    const bool live = unit < (int64_t)D.S0 * nsx * nch;
+    const int64_t strip = live ? unit / nch : 0;
+    const int ck = live ? (int)(unit - strip * nch) : 0;
+    const int t0 = ck * S2 / nch, tlen = live ? (ck + 1) * S2 / nch - t0 : 0;   // ≤ DMF_TC nodes
+    const int iy = (int)(strip / nsx);
+    const int x0 = (int)(strip - (int64_t)iy * nsx) * 64;
+    const int nv = live ? min(64, D.S1 - x0) : 0;
+    double* __restrict__ qc = q + D.col3 + ((int64_t)iy * D.S1 + x0) * S2 + t0;   // entry (node nl, t0 + tt): qc[nl·S2 + tt]
+    double qv[DMF_TC], q2[2];
+    // the lane's entries e = lane + 64k of the chunk's nv × tlen: node nl = ⌊e / tlen⌋ = (e·rt) >> 16
+    // (exact: e < 1024, tlen ≤ 16, so e·(rt·tlen − 2¹⁶) < 2¹⁶)
+    const int rt = tlen ? (65536 + tlen - 1) / tlen : 0;
+#pragma unroll
+    for (int k = 0; k < DMF_TC; ++k) {
+        const int e = lane + 64 * k;
+        const int nl = (e * rt) >> 16;
+        qv[k] = e < nv * tlen ? qc[nl * S2 + (e - nl * tlen)] : 0.0;
+    }
+    const int ix = x0 + lane;
+    const bool mine = live && ix < D.S1;
+    const int64_t nd = (int64_t)iy * D.S1 + ix;
+    const bool two = mine && ck == 0;   // the 2-D parts leave with the strip's first chunk
+#pragma unroll
+    for (int k = 0; k < 2; ++k) q2[k] = two && k < D.n2 ? q[D.col2[k] + nd] : 0.0;
+    double* __restrict__ acc = &LA[w][lane];   // acc[(t − t0)·64]
+#pragma unroll
+    for (int k = 0; k < DMF_TC; ++k) acc[k * 64] = 0.0;
+    if (mine) {
+        const double a2 = dmf_node_gather_chunk(D, cell, pt, td, iy, ix, t0, tlen, acc);
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            if (two && k < D.n2) q[D.col2[k] + nd] = q2[k] + a2;
+    }
+    __syncthreads();   // every lane's chunk is complete
+    const double* __restrict__ L = LA[w];
+#pragma unroll
+    for (int k = 0; k < DMF_TC; ++k) {
+        const int e = lane + 64 * k;
+        if (e < nv * tlen) {
+            const int nl = (e * rt) >> 16, tt = e - nl * tlen;
+            qc[nl * S2 + tt] = qv[k] + L[tt * 64 + nl];
         }
     }
 }
@@ -823,6 +930,9 @@ __global__ __launch_bounds__(BLOCK) void k_cg_ad_xedge(const CgState* __restrict
     else cg_xedge_body<XE_LPC>(cd, coef, p, q, part_e, (int)blockIdx.x - gD);
 }
 
+// ATD = false (lsq_set_cg_tile_dmf): q = N_s p alone; the matrix-free data rows add theirs behind this
+// launch (k_cg_dmf_ad, the elimination, the node gather), and arp, aci, aval, td are not read
+template <bool ATD = true>
 __global__ __launch_bounds__(BLOCK) void k_cg_normal(const CgState* __restrict__ st, const CgDesc* __restrict__ cd,
                                                      const double* __restrict__ coef, const double* __restrict__ z,
                                                      const double* __restrict__ pold, double* __restrict__ pnew,
@@ -883,8 +993,10 @@ __global__ __launch_bounds__(BLOCK) void k_cg_normal(const CgState* __restrict__
             for (int o = 0; o < noff; ++o) acc += cr[o] * L[center + C.loff[o]];
         }
         if (xin) {
-            const int64_t pos = (int64_t)C.node0 + ((int64_t)y * S1 + x) * S2 + t;
-            acc += csr_row_dot(aci, aval, arp[pos], arp[pos + 1], td);
+            if (ATD) {
+                const int64_t pos = (int64_t)C.node0 + ((int64_t)y * S1 + x) * S2 + t;
+                acc += csr_row_dot(aci, aval, arp[pos], arp[pos + 1], td);
+            }
             gam += L[center] * acc;
         }
         qv[k] = acc;
@@ -919,6 +1031,7 @@ __global__ __launch_bounds__(BLOCK) void k_cg_normal(const CgState* __restrict__
 // another workgroup may not have written yet — and only the owned (row, x, t) entries are written
 // back as p, enter q and count in pᵀNp.  The partials leave through the same fixed-order sum as tile
 // mode's, one slot per workgroup.
+template <bool ATD = true>   // as k_cg_normal's
 __global__ __launch_bounds__(BLOCK) void k_cg_normal_chunk(const CgState* __restrict__ st, const CgDesc* __restrict__ cd,
                                                            const double* __restrict__ coef, const double* __restrict__ z,
                                                            const double* __restrict__ pold, double* __restrict__ pnew,
@@ -1022,8 +1135,10 @@ __global__ __launch_bounds__(BLOCK) void k_cg_normal_chunk(const CgState* __rest
             for (int o = 0; o < noff; ++o) acc += cr[o] * L[center + C.loff[o]];
         }
         if (xin) {
-            const int64_t pos = (int64_t)C.node0 + ((int64_t)y * S1 + x) * S2 + t;
-            acc += csr_row_dot(aci, aval, arp[pos], arp[pos + 1], td);
+            if (ATD) {
+                const int64_t pos = (int64_t)C.node0 + ((int64_t)y * S1 + x) * S2 + t;
+                acc += csr_row_dot(aci, aval, arp[pos], arp[pos + 1], td);
+            }
             gam += L[center] * acc;
         }
         qv[k] = acc;
@@ -2191,11 +2306,17 @@ void cg_launch_precond(System& S, const CgGrids& g, int precond) {
 
 // t = Ad·p (+ partials ‖t‖² in column mode): tile mode forms p = z + β p_old on the fly (it runs
 // before the normal kernel), column mode reads the p the normal kernel wrote
-bool cg_use_dmf(const System& S) { return S.cgh.colmode && S.dmf.ok; }
+// (tile and chunk mode under lsq_set_cg_tile_dmf too: cg_tile_dmf)
+bool cg_use_dmf(const System& S) { return S.dmf.ok && (S.cgh.colmode || S.cg_tile_dmf); }
+// tile or chunk mode on matrix-free data rows: column mode's step order around k_cg_normal<false>
+inline bool cg_tile_dmf(const System& S) { return !S.cgh.colmode && cg_use_dmf(S); }
+// the step runs NORMAL, AD, …, ATQ (else tile mode's AD, NORMAL)
+inline bool cg_col_order(const System& S) { return S.cgh.colmode || cg_use_dmf(S); }
 
 // ---- the plain step's stages, in column mode's launch order (DESIGN.md §CGNR, "The step's stages") --
 // q = N p (cg_launch_apply): NORMAL, AD, the elimination's E0 … E3 (elim_nbk), XR_FWD and XR_ATQ
-// (xr_active), ATQ; tile mode runs AD, then NORMAL (which adds ATd·t), and nothing else.  Then
+// (xr_active), ATQ; tile mode runs AD, then NORMAL (which adds ATd·t), and nothing else — unless its data
+// rows are matrix-free (cg_tile_dmf): then column mode's order, without the extra rows.  Then
 // cg_launch_update: ALPHA, PRECOND, BETA.  BEGIN stands before the step's first launch.
 enum CgStage {
     CG_BEGIN, CG_NORMAL, CG_AD, CG_E0, CG_E1, CG_E2, CG_E3, CG_XR_FWD, CG_XR_ATQ, CG_ATQ, CG_ALPHA, CG_PRECOND,
@@ -2234,7 +2355,7 @@ void cg_dmf_prepare(System& S) {
 // the data rows' partials of pᵀNp: Σt² per workgroup, then (biases set) −Σ_j s_j²/D_j, then (extra
 // rows set) their Σt_x² per workgroup
 int cg_nt(const System& S, const CgGrids& g) {
-    return S.cgh.colmode ? g.gD + elim_nbk(S) + (xr_active(S) ? S.xr.nbk : 0) : 0;
+    return cg_col_order(S) ? g.gD + elim_nbk(S) + (xr_active(S) ? S.xr.nbk : 0) : 0;
 }
 
 // extra rows set: t_x = W_x X p and q += Xᵀ W_x t_x, after q = N_s p (and its x-edge correction) and
@@ -2267,9 +2388,11 @@ void cg_launch_data(System& S, const CgGrids& g, const double* pold, const doubl
     cg_launch_bias(S, g, marks);
 }
 
-// k_cg_dmf_atq: 4 strips of 64 nodes per workgroup, the grid a multiple of 8 (xcd_block)
+// k_cg_dmf_atq: 4 strips of 64 nodes per workgroup, the grid a multiple of 8 (xcd_block);
+// k_cg_dmf_atq_long: 4 (strip, chunk of the column) units per workgroup
 dim3 cg_atq_grid(const System& S) {
-    const int64_t strips = (int64_t)S.dmf.S0 * ((S.dmf.S1 + 63) / 64);
+    const int64_t nch = S.dmf.S2 > CG_MAXT ? (S.dmf.S2 + DMF_TC - 1) / DMF_TC : 1;
+    const int64_t strips = (int64_t)S.dmf.S0 * ((S.dmf.S1 + 63) / 64) * nch;
     return dim3((unsigned)(((strips + BLOCK / 64 - 1) / (BLOCK / 64) + 7) / 8 * 8));
 }
 
@@ -2283,9 +2406,12 @@ void cg_launch_dmf_atq(const System& S, const CgState* st, const double* td, dou
     if (S.dmf.S2 <= 12)
         hipLaunchKernelGGL(k_cg_dmf_atq<12>, grid, dim3(BLOCK), 0, S.stream, st, S.dmf, S.dmf_cell.p, P, td, q, ast, apg,
                            ang, apt, ant);
-    else
+    else if (S.dmf.S2 <= CG_MAXT)
         hipLaunchKernelGGL(k_cg_dmf_atq<CG_MAXT>, grid, dim3(BLOCK), 0, S.stream, st, S.dmf, S.dmf_cell.p, P, td, q,
                            ast, apg, ang, apt, ant);
+    else
+        hipLaunchKernelGGL(k_cg_dmf_atq_long, grid, dim3(BLOCK), 0, S.stream, st, S.dmf, S.dmf_cell.p, P, td, q, ast,
+                           apg, ang, apt, ant);
 }
 
 void cg_launch_atdq(System& S) {
@@ -2318,8 +2444,10 @@ void cg_launch_normal(System& S, const CgGrids& g, const double* pold, double* p
             cg_launch_var(S, pnew, S.cg_q.p, S.cg_part_g.p + g.gN + S.cgh.nedge, S.stream, S.cst.p);
         }
     } else {   // tile mode, or its tiles cut along dim 2 too (chunk mode): the same arguments, step and partial slots
-        hipLaunchKernelGGL(S.cgh.chunk ? k_cg_normal_chunk : k_cg_normal, dim3(g.gN), dim3(BLOCK), lds, S.stream, S.cst.p,
-                           S.cgd.p, S.cg_coef.p, S.cg_z.p,
+        const bool atd = !cg_use_dmf(S);   // matrix-free data rows: q = N_s p alone (cg_launch_apply)
+        hipLaunchKernelGGL(S.cgh.chunk ? (atd ? k_cg_normal_chunk<true> : k_cg_normal_chunk<false>)
+                                       : (atd ? k_cg_normal<true> : k_cg_normal<false>),
+                           dim3(g.gN), dim3(BLOCK), lds, S.stream, S.cst.p, S.cgd.p, S.cg_coef.p, S.cg_z.p,
                            pold, pnew, S.cg_q.p, S.ATd.rp.p, S.ATd.ci.p, S.ATd.val.p, S.cg_t.p, S.cg_part_g.p);
         cg_launch_var(S, pnew, S.cg_q.p, S.cg_part_g.p + g.gN, S.stream, S.cst.p);
     }
@@ -2343,7 +2471,7 @@ void cg_launch_beta(System& S, const CgGrids& g, int mode) {
 // q += Adᵀ t.  Tile mode: t alone, k_cg_normal adds ATd·t
 void cg_launch_rows(System& S, const CgGrids& g, const double* pold, const double* pnew, CgMarks* marks = nullptr) {
     cg_launch_data(S, g, pold, pnew, marks);
-    if (!S.cgh.colmode) return;
+    if (!cg_col_order(S)) return;
     cg_launch_xr(S, g, pnew, marks);
     cg_launch_atdq(S);
     cg_mark(marks, CG_ATQ, S.stream);
@@ -2354,7 +2482,7 @@ void cg_launch_rows(System& S, const CgGrids& g, const double* pold, const doubl
 // spellings in cg_launch_iteration); the profilers, the test hook and the ranks of a group follow.
 void cg_launch_apply(System& S, const CgGrids& g, const double* pold, double* pnew, CgMarks* marks = nullptr) {
     cg_mark(marks, CG_BEGIN, S.stream);
-    if (S.cgh.colmode) {   // normal (writes p, q = N_s p) → data (t = Ad p) → q += ATd·t
+    if (cg_col_order(S)) {   // normal (writes p, q = N_s p) → data (t = Ad p) → q += ATd·t
         cg_launch_normal(S, g, pold, pnew);
         cg_mark(marks, CG_NORMAL, S.stream);
         cg_launch_rows(S, g, pold, pnew, marks);
@@ -2382,7 +2510,7 @@ void cg_launch_update(System& S, const CgGrids& g, int precond, CgMarks* marks =
 void cg_launch_iteration(System& S, const CgGrids& g, int ph, int precond) {
     const double* pold = cg_pold(S, ph);
     double* pnew = cg_pnew(S, ph);
-    if (cg_use_dmf(S) && S.cg_var.empty() && S.cgh.pad[1] == 8) {
+    if (S.cgh.colmode && cg_use_dmf(S) && S.cg_var.empty() && S.cgh.pad[1] == 8) {
         // the x-edge correction (q at the dim-1 edge nodes, latency-bound) in the data rows'
         // Ad·p launch (both read p only), then q += Adᵀt with α in the node gather's workgroup 0
         cg_launch_normal(S, g, pold, pnew, false);
@@ -2592,6 +2720,8 @@ void cg_kernel_bytes(const System& S, int precond, double out[3]) {
         if (bias_active(S)) out[0] += bias_step_bytes(S);
         if (sgrid_active(S)) out[0] += sgrid_step_bytes(S);
         out[1] = 32.0 * nf;
+        // tile / chunk mode on these rows: chunk mode's staging term, no stored-row terms
+        if (S.cgh.chunk) out[1] += 16.0 * ((double)cg_chunk_staged(S.cgh) - nf);
     } else if (S.cgh.colmode) {
         // data = Ad·p (12 B/entry, p gathers, t) + ATd·t (entries, row pointers, t gathers, q RMW)
         out[0] = 12.0 * zd + 8.0 * nd + 8.0 * md + 12.0 * zd + 4.0 * ne + 8.0 * md + 16.0 * nd;
@@ -2648,6 +2778,20 @@ bool cg_available(System& S, int precond) {
 void cg_set_chunks(System& S, bool on) {
     if (S.cg_chunks == on) return;
     S.cg_chunks = on;
+    graph_cache_drop(&S);
+    mg_free(S.mg);
+    S.mg = nullptr;
+    S.mg_why.clear();
+    S.cg_ok = false;
+    S.cg_why.clear();
+    S.cg_ready = false;
+}
+
+// lsq_set_cg_tile_dmf: read by build_dmf at the formation (the point table of a long column) and by
+// cg_use_dmf.  A change drops what cg_set_chunks drops.
+void cg_set_tile_dmf(System& S, bool on) {
+    if (S.cg_tile_dmf == on) return;
+    S.cg_tile_dmf = on;
     graph_cache_drop(&S);
     mg_free(S.mg);
     S.mg = nullptr;
@@ -2818,7 +2962,7 @@ void cg_profile(System& S, int reps, int precond, double* out) {
              (S.cgh.chunk ? 8.0 : 0.0);
     cg_kernel_bytes(S, precond, out + 4);
     if (cg_live(S, precond)) {
-        const int rows = S.cgh.colmode ? CG_ATQ : CG_AD;   // the last stage of the data rows' share
+        const int rows = cg_col_order(S) ? CG_ATQ : CG_AD;   // the last stage of the data rows' share
         double ms[CG_NSTAGE];
         cg_profile_steps(S, reps, precond,
                          cg_bit(CG_BEGIN) | cg_bit(CG_NORMAL) | cg_bit(rows) | cg_bit(CG_ALPHA) | cg_bit(CG_PRECOND) |

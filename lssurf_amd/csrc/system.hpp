@@ -163,6 +163,10 @@ constexpr int CG_MAXI = 16;                 // (row, dim-2) items per wave of on
 // the template width MAXT with zeros), so the loops are fully unrolled and branch-free.  A
 // workgroup streams a strip of ty rows through an LDS ring (lsqr_cg.inc, cg_strip).
 constexpr int CG_MAXT = 16;
+// Matrix-free data rows under lsq_set_cg_tile_dmf: the longest dim-2 column (tile / chunk mode's cap);
+// k_cg_dmf_atq_long cuts such a column into chunks of ≤ DMF_TC nodes, a wave each
+constexpr int DMF_MAXT_LONG = 64;
+constexpr int DMF_TC = 16;
 constexpr int CG_MAX_GRP = 49;
 constexpr int CG_NCW = 16;                  // ring staging: row-image columns per lane (a wave stages whole rows: ≤ 1024)
 // Node-block factors R_b⁻¹ as the CG update and the multigrid smoother stream them: bf16 (the
@@ -610,6 +614,7 @@ struct System {
     // row scales change; vectors in the full column space
     bool cg_ok = false;            // the structured normal operator exists for this system
     bool cg_chunks = false;        // lsq_set_cg_chunks: chunk mode where a tile-mode image exceeds LDS
+    bool cg_tile_dmf = false;      // lsq_set_cg_tile_dmf: tile / chunk mode on matrix-free data rows, column mode's step order
     int64_t cg_data_cols = 0;      // columns touched by the data rows
     DmfDesc dmf{};                  // matrix-free data rows for CGNR (ok = 0: use Ad / ATd)
     DBuf<double> dmf_pt;            // per sorted point: f_y, f_x, f_t, row scale (double4)

@@ -36,6 +36,12 @@ lsq_E_method='window', and 'auto' above errors.WINDOW_MIN_COLS columns, run with
 windows on the grid-only system plus one CGNR solve per bias column (lsq_cov_border_solved,
 errors.calc_and_parse_errors); 'band' and 'dense' are unchanged, and sensor bias grids, priors and
 n_gpus > 1 stay refused.
+lsq_tile_eliminate=True lets lsq_bias='eliminate' (and 'auto') run on dz grids of 16 to 19 epochs, and
+together with lsq_cg_chunks=True of 20 to 64: tile and chunk mode then take matrix-free data rows
+(lsq_set_cg_tile_dmf) and eliminate biases, slopes and sensor grids as below 16 epochs, with block-Jacobi;
+timing['tile_eliminate'] says whether the last solve ran so.  Still refused with the key: the multigrid,
+priors beside 'eliminate', n_gpus > 1, more than 64 epochs, 20 or more epochs without lsq_cg_chunks; the
+compute_E rules above are unchanged.
 """
 from time import ctime, time
 
@@ -89,7 +95,12 @@ DEFAULTS = {'reference_epoch': 0, 'W_ctr': 1e4, 'return_fit_objects': False, 'ma
             'lsq_sgrid_joint': False,
             # CGNR on dz grids of 20 to 64 epochs: the normal operator's tiles cut along time too (chunk
             # mode) instead of method 1 falling back to LSQR (opt-in; below 20 epochs the key does nothing)
-            'lsq_cg_chunks': False}
+            'lsq_cg_chunks': False,
+            # eliminated biases, slopes and sensor grids on dz grids of 16 to 64 epochs: tile and chunk mode
+            # on matrix-free data rows (opt-in; 20 and more epochs need lsq_cg_chunks too; below 16 epochs the
+            # key does nothing).  Still refused there: multigrid, priors beside 'eliminate', n_gpus > 1, more
+            # than 64 epochs; the compute_E rules are unchanged
+            'lsq_tile_eliminate': False}
 
 OUT_OF_SCOPE = ('lagrangian_coords', 'constraint_scaling_maps', 'mask_file', 'bias_edit_vals')
 
@@ -100,8 +111,13 @@ class FitSystem:
 
     def __init__(self, G_data, Gc, keep_cols, n_full, device=0, structured=True, grids=None, bias=None,
                  extra_ops=None, extra_csr=None, extra_mg=False, sensor_grids=None, joint=False, iterative=True,
-                 cg_chunks=False):
-        """cg_chunks: CGNR's chunk mode (LSQSolver.set_cg_chunks), set before the formation: a dz grid of
+                 cg_chunks=False, tile_dmf=False):
+        """tile_dmf: tile and chunk mode on matrix-free data rows (LSQSolver.set_cg_tile_dmf), set before the
+        formation: with a dz grid of 16 to 19 epochs, or of 20 to 64 beside cg_chunks, bias and sensor_grids
+        are then eliminated as below 16 epochs and this constructor's cg_available question passes.
+        Multigrid stays refused there, extra rows take the COO path, and 20 or more epochs without
+        cg_chunks, or more than 64, still have no CGNR operator.
+        cg_chunks: CGNR's chunk mode (LSQSolver.set_cg_chunks), set before the formation: a dz grid of
         20 to 64 epochs then runs method 1 as CGNR instead of falling back to LSQR.  What tile mode
         refuses stays refused: no multigrid, no eliminated bias / sensor_grids (this constructor raises),
         extra rows take the COO path.
@@ -144,6 +160,9 @@ class FitSystem:
         self.cg_chunks = bool(cg_chunks)
         if self.cg_chunks:
             self.solver.set_cg_chunks(True)
+        self.tile_dmf = bool(tile_dmf)
+        if self.tile_dmf:
+            self.solver.set_cg_tile_dmf(True)
         self.solver.set_col_map(self.n_full, keep_cols)
         m = self.n_data + self.n_con
         extra_ops = list(extra_ops or [])
@@ -200,6 +219,8 @@ class FitSystem:
                 self.solver = LSQSolver(device)
                 if self.cg_chunks:
                     self.solver.set_cg_chunks(True)
+                if self.tile_dmf:
+                    self.solver.set_cg_tile_dmf(True)
                 self.solver.set_col_map(self.n_full, keep_cols)
                 desc = None
         self.desc = desc           # the descriptors (bench.py's structured CPU baseline reads them)
@@ -528,6 +549,11 @@ def iterate_fit(data, system, rhs, TCinv, G_data, Gc, in_TSE, timing, args, grid
         # did this solve run CGNR in chunk mode (lsq_cg_chunks on a dz grid of 20 to 64 epochs)?
         timing['cg_chunks'] = bool(getattr(system, 'cg_chunks', False) and system.stats['method'] == 1 and
                                    system.solver.cg_layout_info()['mode'] == 'chunk')
+        # did this solve eliminate biases or sensor grids in tile or chunk mode (lsq_tile_eliminate, 16 to 64 epochs)?
+        timing['tile_eliminate'] = bool(
+            getattr(system, 'tile_dmf', False) and system.stats['method'] == 1 and
+            (getattr(system, 'bias_ids', None) is not None or getattr(system, 'sg', None) is not None) and
+            system.solver.cg_layout_info()['mode'] in ('tile', 'chunk'))
         prev_solve = (weight, np.asarray(in_TSE, bool).copy() if opts['precond'] == 4 else None)
         system.last_x = x   # compact solution: z_est and the constraint statistics read it, not m0
         timing['sparseqr_solve'] = time() - tic
@@ -789,14 +815,16 @@ def _bias_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, bias_model, m
             bias += ((group, u, np.full((len(slope_dict), 2), 1. / (bias_model['E_slope_bias'] * SLOPE_RESCALE))),)
         try:
             return FitSystem(G_grid, Gc_grid, keep_cols[keep_cols < n_grid], n_grid, device=device, grids=grids,
-                             bias=bias, sensor_grids=sg, joint=sg is not None, cg_chunks=args['lsq_cg_chunks'])
+                             bias=bias, sensor_grids=sg, joint=sg is not None, cg_chunks=args['lsq_cg_chunks'],
+                             tile_dmf=args['lsq_tile_eliminate'])
         except NativeError as e:
             if mode == 'eliminate':
                 raise
             if sg is not None:
                 warnings.warn(f"smooth_fit: lsq_bias='auto' with lsq_sgrid_joint takes 'columns': the device refuses "
                               f"the joint elimination ({e})", RuntimeWarning, stacklevel=3)
-    return FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=device, grids=grids, cg_chunks=args['lsq_cg_chunks'])
+    return FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=device, grids=grids, cg_chunks=args['lsq_cg_chunks'],
+                     tile_dmf=args['lsq_tile_eliminate'])
 
 
 def _sgrid_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, sgrid_sensor, constraint_op_list, mode, grids,
@@ -817,11 +845,13 @@ def _sgrid_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, sgrid_sensor
         sg = sensor_grid_device_form(data, grids, sgrid_sensor, constraint_op_list)
         try:
             return FitSystem(G_grid, Gc_grid, keep_cols[keep_cols < n_grid], n_grid, device=device, grids=grids,
-                             sensor_grids=sg, cg_chunks=args['lsq_cg_chunks'])
+                             sensor_grids=sg, cg_chunks=args['lsq_cg_chunks'],
+                             tile_dmf=args['lsq_tile_eliminate'])
         except NativeError:
             if mode == 'eliminate':
                 raise
-    return FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=device, grids=grids, cg_chunks=args['lsq_cg_chunks'])
+    return FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=device, grids=grids, cg_chunks=args['lsq_cg_chunks'],
+                     tile_dmf=args['lsq_tile_eliminate'])
 
 
 def smooth_fit(**kwargs):
@@ -854,6 +884,8 @@ def smooth_fit(**kwargs):
         raise ValueError(f"smooth_fit: lsq_sgrid_joint must be True or False, not {args['lsq_sgrid_joint']!r}")
     if not isinstance(args['lsq_cg_chunks'], (bool, np.bool_)):
         raise ValueError(f"smooth_fit: lsq_cg_chunks must be True or False, not {args['lsq_cg_chunks']!r}")
+    if not isinstance(args['lsq_tile_eliminate'], (bool, np.bool_)):
+        raise ValueError(f"smooth_fit: lsq_tile_eliminate must be True or False, not {args['lsq_tile_eliminate']!r}")
     bias_mode = args['lsq_bias']
     if args['bias_params'] is not None:
         if bias_mode is None:
@@ -1100,7 +1132,8 @@ def smooth_fit(**kwargs):
                                                           keep_cols.size <= args['lsq_dense_max'])
                 system = FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=devices[0], grids=grids,
                                    extra_ops=prior_ops, extra_mg=bool(args['lsq_prior_mg']) and bool(prior_ops),
-                                   iterative=not dense, cg_chunks=args['lsq_cg_chunks'])
+                                   iterative=not dense, cg_chunks=args['lsq_cg_chunks'],
+                                   tile_dmf=args['lsq_tile_eliminate'])
             if b_rows_all is not None and not getattr(system, 'n_extra', 0):
                 b_rows = max(b_rows, b_rows_all)
             if b_rows_sg is not None and getattr(system, 'sg', None) is None:

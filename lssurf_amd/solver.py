@@ -251,6 +251,14 @@ class LSQSolver:
         d['normal_mode'] = 'column' if int(o[7]) & 4 else 'chunk' if int(o[7]) & 8 else 'tile'
         return d
 
+    def set_cg_tile_dmf(self, on=True):
+        """Tile and chunk mode on matrix-free data rows (lsq_set_cg_tile_dmf), set BEFORE the formation:
+        a dz grid of 16 to 64 epochs (20 and more with set_cg_chunks) then runs CGNR's step in column
+        mode's order, and data biases, slopes and sensor grids are eliminated there as they are below
+        16 epochs.  Multigrid and extra rows stay refused in tile and chunk mode.  Single-GPU handles
+        only."""
+        self._check(self._L.lsq_set_cg_tile_dmf(self._h, 1 if on else 0), 'lsq_set_cg_tile_dmf')
+
     def set_cg_chunks(self, on=True):
         """Chunk mode for CGNR (lsq_set_cg_chunks): grids of 20 to 64 nodes along their last dimension,
         whose tile-mode image exceeds LDS, get tiles that are also cut along that dimension instead of

@@ -41,6 +41,9 @@ CONFIGS = {
     'c3z': (512, 12, 1_000_000),
     # C4's lattice with 28 epochs (seven years of quarterly epochs): CGNR's chunk mode (tools/chunk_step.py)
     'c4t28': (1024, 28, 2_000_000),
+    # smaller lattices with 28 epochs (tools/tile_elim_step.py: its triplet-formed 'columns' leg)
+    't64t28': (64, 28, 8_192),
+    'c3t28': (512, 28, 500_000),
 }
 # seed offset of each config's points (default_rng(20251121 + id)): the configs' positions in
 # CONFIGS when round 4 started, frozen — round 3 derived the offset from the dict position, so
@@ -48,7 +51,7 @@ CONFIGS = {
 # between two builds that solve the same system alike).  New configs take new ids.
 SEED_ID = {'c1': 0, 'c3': 1, 'c4': 2, 'c5': 3, 't64': 4, 't256': 5, 't128': 6, 'tdense': 7, 't15': 8,
            'c4y4': 9, 'c4y8': 10, 'c5a': 11, 'ta64': 12, 'ta100': 13, 't64z': 14, 'c3z': 15, 'c5y8': 16,
-           'c4t28': 17}
+           'c4t28': 17, 't64t28': 18, 'c3t28': 19}
 ANISO = ('c5a', 'ta64', 'ta100')
 Z0_REFINED = ('t64z', 'c3z')
 
