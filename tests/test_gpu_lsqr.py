@@ -59,17 +59,23 @@ def test_lsqr_matches_exact_solution(gpu_available, name):
 
 @pytest.mark.parametrize('name', ['sf3d', 'nb_xt'])
 def test_spmv_bitwise_vs_scipy(gpu_available, name):
+    """G x and Gᵀ u of the formed CSR and its transpose: k_csr_spmv sums a row's entries in index
+    order from 0, one thread per row, as scipy's CSR product does, so both equal scipy's bit for bit."""
     g, S, sysm, w, rhs = _fit_system(name)
     rng = np.random.default_rng(1)
     x = rng.normal(size=sysm.solver.n)
     y = sysm.solver.spmv(x)
-    yt = sysm.solver.spmv(rng.normal(size=sysm.solver.m), trans=True)
+    u = rng.normal(size=sysm.solver.m)
+    yt = sysm.solver.spmv(u, trans=True)
     sysm.close()
     G = sp.vstack([S['G_data'].toCSR(), S['Gc'].toCSR()]).tocsr()
     G = sp.csr_matrix(G[:, sysm.keep_cols])
     G.sort_indices()
     np.testing.assert_array_equal(y, G.dot(x))
+    GT = sp.csr_matrix(G.T)
+    GT.sort_indices()
     assert yt.shape == (sysm.solver.n,)
+    np.testing.assert_array_equal(yt, GT.dot(u))
 
 
 def test_gpu_cpu_lsqr_agree(gpu_available):
