@@ -463,6 +463,13 @@ int lsq_vgroup_iterate(lsq_vgroup* g, const double* const* b, int64_t iters, con
                        lsq_stats* s);
 const char* lsq_vgroup_last_error(lsq_vgroup* g);
 void lsq_vgroup_destroy(lsq_vgroup* g);
+/* Test hook: what rank `rank` of the group holds from its last multigrid solve (method 1, precond 4).
+ * out[0] = levels L, out[1] = lp (levels 1 ... lp are partitioned over the ranks, the rest replicated),
+ * then per level l three values: the smoother's lambda of that solve's set-up (0 for the coarsest level),
+ * and the node rows [oa, ob) of the level the rank owns (level 0: of the global fine lattice).  cap must
+ * hold 2 + 3L values.  Reads state only: no set-up, no solve path changes.  Returns the count written,
+ * or -1 with the reason in lsq_vgroup_last_error (no multigrid solve yet, rank out of range, cap). */
+int lsq_vgroup_mg_info(lsq_vgroup* g, int32_t rank, double* out, int64_t cap);
 
 /* Device group: the distributed solve over N distinct devices from ONE process (smooth_fit's
  * n_gpus; SURVEY.md §8(b) "ranks invisible to Python").  One RCCL communicator per device

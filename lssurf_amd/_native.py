@@ -61,7 +61,7 @@ EXPORTS = ['lsq_default_opts', 'lsq_create', 'lsq_destroy', 'lsq_last_error', 'l
            'lsq_solve', 'lsq_spmv', 'lsq_spmv_rows', 'lsq_rows_sumsq', 'lsq_data_colsum', 'lsq_iterate', 'lsq_profile_kernels', 'lsq_cg_available', 'lsq_profile_cg', 'lsq_set_cg_chunks', 'lsq_set_cg_tile_dmf', 'lsq_cg_layout_info', 'lsq_mg_info', 'lsq_mg_apply', 'lsq_normal_apply', 'lsq_set_data_bias', 'lsq_get_data_bias', 'lsq_set_data_slope', 'lsq_get_data_slope', 'lsq_profile_data_slope', 'lsq_set_sensor_grids', 'lsq_set_sensor_grids_joint', 'lsq_get_sensor_grids', 'lsq_profile_sensor_grids', 'lsq_sell_info', 'lsq_sigma_x', 'lsq_cov_band', 'lsq_cov_band_bordered', 'lsq_cov_border_solved', 'lsq_cov_band_window', 'lsq_cov_band_windows', 'lsq_cov_band_windows_schur', 'lsq_set_band_order', 'lsq_band_factor',
            'lsq_get_rinv', 'lsq_dist_unique_id', 'lsq_create_dist', 'lsq_dist_comm_info', 'lsq_dist_referenced_cols',
            'lsq_dist_set_layout', 'lsq_dist_set_halo', 'lsq_dist_set_global', 'lsq_vgroup_create', 'lsq_vgroup_rank', 'lsq_vgroup_solve', 'lsq_vgroup_iterate',
-           'lsq_vgroup_last_error', 'lsq_vgroup_destroy',
+           'lsq_vgroup_last_error', 'lsq_vgroup_destroy', 'lsq_vgroup_mg_info',
            'lsq_dgroup_create', 'lsq_dgroup_rank', 'lsq_dgroup_solve', 'lsq_dgroup_iterate', 'lsq_dgroup_last_error',
            'lsq_dgroup_destroy', 'lsq_fence_selftest',
            'lsq_rde_create', 'lsq_rde_order_stats', 'lsq_rde_last_error', 'lsq_rde_destroy',
@@ -150,6 +150,7 @@ def load():
         'lsq_vgroup_iterate': ([P, P, i64, P, P], ctypes.c_int),
         'lsq_vgroup_last_error': ([P], ctypes.c_char_p),
         'lsq_vgroup_destroy': ([P], None),
+        'lsq_vgroup_mg_info': ([P, i32, P, i64], ctypes.c_int),
         'lsq_dgroup_create': ([i32, P], P),
         'lsq_dgroup_rank': ([P, i32], P),
         'lsq_dgroup_solve': ([P, P, P, P, P], ctypes.c_int),

@@ -1215,6 +1215,15 @@ int lsq_vgroup_iterate(lsq_vgroup* g, const double* const* b, int64_t iters, con
     });
 }
 
+int lsq_vgroup_mg_info(lsq_vgroup* g, int32_t rank, double* out, int64_t cap) {
+    if (g && g->G.ranks.empty()) {   // before the first solve: nothing to read, and no set-up from here
+        g->err = "lsq_vgroup_mg_info: no multigrid solve (precond 4) on this group yet";
+        return -1;
+    }
+    const int rc = vguarded(g, [&](lsq::Group& G) { return lsq::group_mg_info(G, rank, out, cap); });
+    return rc < 0 ? -1 : rc;
+}
+
 }  // extern "C"
 
 // ---- device group: N devices driven from one process (smooth_fit(n_gpus=N)) ------------------

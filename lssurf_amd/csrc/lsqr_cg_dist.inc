@@ -847,3 +847,27 @@ int group_cg_iterate(Group& G, const double* const* h_b, int64_t iters, const ls
     group_cg_stats(G, h, precond, ms, stats);
     return 0;
 }
+
+// lsq_vgroup_mg_info: what rank r's hierarchy holds after the last multigrid solve — out[0] = levels L,
+// out[1] = lp, then per level (λ of the last set-up; 0 for the coarsest, which has no smoother), the
+// rank's owned node rows oa, ob (level 0: of the global fine lattice).  Reads state only: no set-up,
+// no kernel.  Returns the count written.
+int group_mg_info(Group& G, int rank, double* out, int64_t cap) {
+    if (rank < 0 || rank >= (int)G.ranks.size()) throw std::invalid_argument("lsq_vgroup_mg_info: rank out of range");
+    System& S = *G.ranks[rank];
+    if (!S.mg || !S.mg->dist) throw std::invalid_argument("lsq_vgroup_mg_info: no multigrid solve (precond 4) on this group yet");
+    const MgHier& H = *S.mg;
+    const int64_t L = (int64_t)H.lev.size();
+    if (!out || cap < 2 + 3 * L) throw std::invalid_argument("lsq_vgroup_mg_info: output too small");
+    std::vector<double> lam((size_t)L, 0.0);
+    HIP_CHECK(hipMemcpyAsync(lam.data(), H.lam.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost, S.stream));
+    HIP_CHECK(hipStreamSynchronize(S.stream));
+    out[0] = (double)L;
+    out[1] = (double)H.lp;
+    for (int64_t l = 0; l < L; ++l) {
+        out[2 + 3 * l] = H.lev[l].coarsest ? 0.0 : lam[l];
+        out[3 + 3 * l] = (double)(l ? H.lev[l].oa : H.oa);
+        out[4 + 3 * l] = (double)(l ? H.lev[l].ob : H.ob);
+    }
+    return (int)(2 + 3 * L);
+}

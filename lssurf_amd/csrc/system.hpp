@@ -710,6 +710,7 @@ int group_solve(Group& G, const double* const* h_b, double* const* h_x, const ls
 int group_iterate(Group& G, const double* const* h_b, int64_t iters, const lsq_opts& o, lsq_stats* stats);
 int group_cg_solve(Group& G, const double* const* h_b, double* const* h_x, const lsq_opts& o, lsq_stats* stats);
 int group_cg_iterate(Group& G, const double* const* h_b, int64_t iters, const lsq_opts& o, lsq_stats* stats);
+int group_mg_info(Group& G, int rank, double* out, int64_t cap);   // lsq_vgroup_mg_info (lsqr_cg_dist.inc)
 void referenced_cols(System& S, uint8_t* h_flags);
 void relabel_columns(System& S, const int32_t* h_map, int64_t n_local);
 

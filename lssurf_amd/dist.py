@@ -659,6 +659,7 @@ class VirtualDistFitSystem(_Base):
         st = LsqStats()
         self._check(self._fn('solve')(self.g, bp, xp, ctypes.byref(o), ctypes.byref(st)), f'{self._api}_solve')
         self.stats = st.as_dict()
+        self.x_local = xs   # per rank, what the library returned: its local columns (tests)
         x = np.zeros(self.keep_cols.size)
         for r, xr in enumerate(xs):
             if self.structured:
@@ -675,6 +676,19 @@ class VirtualDistFitSystem(_Base):
         self._check(self._fn('iterate')(self.g, bp, int(iters), ctypes.byref(o), ctypes.byref(st)),
                     f'{self._api}_iterate')
         return st.as_dict()
+
+    def mg_info(self, rank):
+        """What `rank` holds from the group's last multigrid solve (lsq_vgroup_mg_info; virtual groups):
+        dict(levels, lp, lam, oa, ob) — lp: levels 1 … lp are partitioned over the ranks; per level the λ
+        of that solve's set-up (0 on the coarsest) and the node rows [oa, ob) the rank owns."""
+        if self._api != 'lsq_vgroup':
+            raise NotImplementedError('mg_info reads a virtual group')
+        out = np.zeros(2 + 3 * 32)
+        n = self.L.lsq_vgroup_mg_info(self.g, int(rank), ptr(out), out.size)
+        self._check(n, 'lsq_vgroup_mg_info')
+        L = int(out[0])
+        per = out[2:2 + 3 * L].reshape(L, 3)
+        return dict(levels=L, lp=int(out[1]), lam=per[:, 0].copy(), oa=per[:, 1].astype(int), ob=per[:, 2].astype(int))
 
     def close(self):
         if getattr(self, 'g', None):

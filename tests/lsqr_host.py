@@ -78,13 +78,15 @@ def _sym_ortho(a, b):
 DEFECTS = ('mt_swap', 'stale_v', 'cs_twice')
 
 
-def lsqr(A, b, factors, kmax, x0=None, dtype=np.float64, defect=None):
+def lsqr(A, b, factors, kmax, x0=None, dtype=np.float64, defect=None, stale_cols=None):
     """kmax steps of LSQR on min ‖A M y − (b − A x0)‖, x_k = x0 + M y_k.  Returns a dict: x
     (kmax + 1, n) with x[k] the iterate after k steps, and per scalar of SCALARS an array (kmax + 1)
     with entry k the value scipy.sparse.linalg.lsqr(A·M, b − A x0, iter_lim=k) returns (entry 0:
     the set-up's; xnorm is ‖y_k‖, the correction in the preconditioned coordinates).
     defect (the sensitivity tests alone): 'mt_swap' applies R̃ where R̃ᵀ belongs in the Aᵀ leg,
-    'stale_v' forms w_{k+1} from the ṽ of the step before, 'cs_twice' applies M twice in the A leg."""
+    'stale_v' forms w_{k+1} from the ṽ of the step before (stale_cols, a column mask: on those columns
+    alone — tests/dist_host.py: a rank's ghost copies left unexchanged), 'cs_twice' applies M twice in
+    the A leg."""
     assert defect is None or defect in DEFECTS
     A = sp.csr_matrix(A).astype(dtype)
     AT = A.T.tocsr()
@@ -136,7 +138,7 @@ def lsqr(A, b, factors, kmax, x0=None, dtype=np.float64, defect=None):
         t1, t2 = phi / rho, -theta / rho
         ddnorm = ddnorm + (w @ w) / (rho * rho)
         y = y + t1 * w
-        w = (v_prev if defect == 'stale_v' else v) + t2 * w
+        w = ((v_prev if stale_cols is None else np.where(stale_cols, v_prev, v)) if defect == 'stale_v' else v) + t2 * w
         delta = sn2 * rho
         gambar = -cs2 * rho
         rhs = phi - delta * z
