@@ -572,6 +572,29 @@ int lsq_set_cg_chunks(lsq_handle* h, int32_t on);
  * Default: off. */
 int lsq_set_cg_tile_dmf(lsq_handle* h, int32_t on);
 int lsq_cg_layout_info(lsq_handle* h, int64_t* out8);
+/* Per-row constraint scales inside CGNR.  A stencil part whose rows do not share one row scale
+ * (weight × row mask) — the constraint rows of a masked fit, or of one with constraint scaling maps —
+ * has no class-table normal stencil: lsq_cg_available is 0 ("a stencil part has per-row scales …")
+ * and method 1 falls back to LSQR.  lsq_set_cg_scaled(h, 1) keeps such a part in the matrix-free
+ * CGNR operator when its scale is one value per (y, x) node: the part is left out of the class table
+ * and applied by k_cg_scaled from a squared-scale field over its (y, x) centre box, rebuilt from the
+ * row scales whenever they are refreshed.  Refused with the key too (lsq_cg_available 0, the reason
+ * names the part): scales that differ in any bit along the last dimension at one node, a reach beyond
+ * ±2 in y or x, tile and chunk mode (16 nodes and more along the last dimension), ranks of a
+ * distributed, virtual or device group; precond 4 is refused with "multigrid: per-row constraint
+ * scales".  Systems whose parts all share one scale, and every system without the key, run exactly
+ * as before.  Callable any time after lsq_create; a change drops the CGNR description, the captured
+ * iterations and the multigrid levels.  Returns −2 on a rank of a distributed, virtual or device
+ * group.  Default: off.
+ * lsq_cg_scaled_info builds the description if needed: out4 = {scaled parts, bytes of their fields,
+ * grids with scaled parts, workgroups of their launches} (zeros without the key or the operator).
+ * lsq_profile_cg_scaled: after lsq_iterate with the same precond (its live state), reps more real
+ * iterations with device events around k_cg_scaled: out4 = {ms of its launches per step, their
+ * algorithmic bytes (24 B per column of the grids with scaled parts + 8 B per part and node of
+ * field), ms of the normal kernel and the x-edge pass in front of them, ms of the whole step}. */
+int lsq_set_cg_scaled(lsq_handle* h, int32_t on);
+int lsq_cg_scaled_info(lsq_handle* h, int64_t* out4);
+int lsq_profile_cg_scaled(lsq_handle* h, int32_t reps, int32_t precond, double* out4);
 /* Multigrid (precond 4) test hooks.  lsq_mg_info: out[0] = levels L, then per level
  * (S0, S1, n_full, removed epoch) — cap must hold 1 + 4L values.  lsq_mg_apply on level l's full
  * column space (z0 grid then dz grid, in the system's order): what 0: y = N_l x (level 0: AᵀA;

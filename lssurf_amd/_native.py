@@ -58,7 +58,7 @@ EXPORTS = ['lsq_default_opts', 'lsq_create', 'lsq_destroy', 'lsq_last_error', 'l
            'lsq_profile_extra_rows', 'lsq_set_row_weight',
            'lsq_set_row_mask',
            'lsq_set_column_blocks', 'lsq_set_column_blocks_affine', 'lsq_shape', 'lsq_get_csr', 'lsq_release_full_csr',
-           'lsq_solve', 'lsq_spmv', 'lsq_spmv_rows', 'lsq_rows_sumsq', 'lsq_data_colsum', 'lsq_iterate', 'lsq_profile_kernels', 'lsq_cg_available', 'lsq_profile_cg', 'lsq_set_cg_chunks', 'lsq_set_cg_tile_dmf', 'lsq_cg_layout_info', 'lsq_mg_info', 'lsq_mg_apply', 'lsq_normal_apply', 'lsq_set_data_bias', 'lsq_get_data_bias', 'lsq_set_data_slope', 'lsq_get_data_slope', 'lsq_profile_data_slope', 'lsq_set_sensor_grids', 'lsq_set_sensor_grids_joint', 'lsq_get_sensor_grids', 'lsq_profile_sensor_grids', 'lsq_sell_info', 'lsq_sigma_x', 'lsq_cov_band', 'lsq_cov_band_bordered', 'lsq_cov_border_solved', 'lsq_cov_band_window', 'lsq_cov_band_windows', 'lsq_cov_band_windows_schur', 'lsq_set_band_order', 'lsq_band_factor',
+           'lsq_solve', 'lsq_spmv', 'lsq_spmv_rows', 'lsq_rows_sumsq', 'lsq_data_colsum', 'lsq_iterate', 'lsq_profile_kernels', 'lsq_cg_available', 'lsq_profile_cg', 'lsq_set_cg_chunks', 'lsq_set_cg_tile_dmf', 'lsq_cg_layout_info', 'lsq_set_cg_scaled', 'lsq_cg_scaled_info', 'lsq_profile_cg_scaled', 'lsq_mg_info', 'lsq_mg_apply', 'lsq_normal_apply', 'lsq_set_data_bias', 'lsq_get_data_bias', 'lsq_set_data_slope', 'lsq_get_data_slope', 'lsq_profile_data_slope', 'lsq_set_sensor_grids', 'lsq_set_sensor_grids_joint', 'lsq_get_sensor_grids', 'lsq_profile_sensor_grids', 'lsq_sell_info', 'lsq_sigma_x', 'lsq_cov_band', 'lsq_cov_band_bordered', 'lsq_cov_border_solved', 'lsq_cov_band_window', 'lsq_cov_band_windows', 'lsq_cov_band_windows_schur', 'lsq_set_band_order', 'lsq_band_factor',
            'lsq_get_rinv', 'lsq_dist_unique_id', 'lsq_create_dist', 'lsq_dist_comm_info', 'lsq_dist_referenced_cols',
            'lsq_dist_set_layout', 'lsq_dist_set_halo', 'lsq_dist_set_global', 'lsq_vgroup_create', 'lsq_vgroup_rank', 'lsq_vgroup_solve', 'lsq_vgroup_iterate',
            'lsq_vgroup_last_error', 'lsq_vgroup_destroy', 'lsq_vgroup_mg_info',
@@ -108,6 +108,9 @@ def load():
         'lsq_set_cg_chunks': ([P, i32], ctypes.c_int),
         'lsq_set_cg_tile_dmf': ([P, i32], ctypes.c_int),
         'lsq_cg_layout_info': ([P, P], ctypes.c_int),
+        'lsq_set_cg_scaled': ([P, i32], ctypes.c_int),
+        'lsq_cg_scaled_info': ([P, P], ctypes.c_int),
+        'lsq_profile_cg_scaled': ([P, i32, i32, P], ctypes.c_int),
         'lsq_mg_info': ([P, P, i64], ctypes.c_int),
         'lsq_mg_apply': ([P, i32, i32, P, P], ctypes.c_int),
         'lsq_normal_apply': ([P, P, P], ctypes.c_int),

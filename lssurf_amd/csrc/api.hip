@@ -17,6 +17,9 @@ void cg_profile(System& S, int reps, int precond, double* out);
 void cg_set_chunks(System& S, bool on);
 void cg_set_tile_dmf(System& S, bool on);
 void cg_layout_info(System& S, int64_t* out8);
+void cg_set_scaled(System& S, bool on);
+void cg_scaled_info(System& S, int64_t* out4);
+void cg_profile_scaled(System& S, int reps, int precond, double* out4);
 void cg_profile_xr(System& S, int reps, int precond, double* out);
 void cg_apply_normal(System& S, const double* h_p, double* h_q);
 void cg_data_colsum(System& S, const double* h_f, double* h_out);
@@ -550,6 +553,35 @@ int lsq_set_cg_tile_dmf(lsq_handle* h, int32_t on) {
             return fail(S, "lsq_set_cg_tile_dmf: tile and chunk mode are single-GPU; a rank of a distributed, virtual or "
                            "device group runs the column-mode operator");
         lsq::cg_set_tile_dmf(S, on != 0);
+        return 0;
+    });
+}
+
+int lsq_set_cg_scaled(lsq_handle* h, int32_t on) {
+    return guarded(h, [&](lsq::System& S) {
+        if (S.dist || S.virt || S.comm || S.nranks > 1)
+            return fail(S, "lsq_set_cg_scaled: scaled parts are single-GPU; a rank of a distributed, virtual or device "
+                           "group keeps LSQR where a part has per-row scales");
+        lsq::cg_set_scaled(S, on != 0);
+        return 0;
+    });
+}
+
+int lsq_cg_scaled_info(lsq_handle* h, int64_t* out4) {
+    return guarded(h, [&](lsq::System& S) {
+        if (!S.G.rp.p) return fail(S, "lsq_cg_scaled_info: no matrix");
+        if (!out4) return fail(S, "lsq_cg_scaled_info: null output");
+        lsq::cg_scaled_info(S, out4);
+        return 0;
+    });
+}
+
+int lsq_profile_cg_scaled(lsq_handle* h, int32_t reps, int32_t precond, double* out4) {
+    return guarded(h, [&](lsq::System& S) {
+        if (!S.G.rp.p) return fail(S, "lsq_profile_cg_scaled: no matrix");
+        if (!out4) return fail(S, "lsq_profile_cg_scaled: null output");
+        lsq::graph_cache_drop(&S);
+        lsq::cg_profile_scaled(S, reps > 0 ? reps : 10, precond, out4);
         return 0;
     });
 }

@@ -838,6 +838,7 @@ void scaling_fill_values(System& S, int precond, bool set_csf) {
         S.mfd.upload(&S.mfh, 1, st);
     }
     S.rs_dirty = false;
+    S.rs_gen += 1;
     S.cs_mode = precond;
     S.iter_ready = false;
 }

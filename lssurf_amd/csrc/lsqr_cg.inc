@@ -1568,8 +1568,116 @@ size_t cg_var_lds(const CgVar& V) {
     return sizeof(double) * ((size_t)(CGV_TY + 4 * R) * (CGV_TX + 4 * R) + (size_t)NC * (1 + V.nfield));
 }
 
-// q += A_vᵀA_v p for every field-valued part (partials at part + V.blk0)
-void cg_launch_var(const System& S, const double* p, double* q, double* part, hipStream_t st, const CgState* cst) {
+// Stencil parts with a row scale per (y, x) node on 2-D and 3-D grids (system.hpp CgSc; lsq_set_cg_scaled:
+// the constraint rows of a masked fit or of constraint_scaling_maps), k_cg_var2d's counterpart.  One
+// workgroup per tile of G.ty × CGS_TX nodes × the whole dim-2 column; for each scaled part of the grid
+//   t_c  = W2(c) Σ_e v_e p[c + o_e]          at the centres of the tile and its R halo (0 outside the box),
+//   q_i += Σ_e v_e t_{i − o_e}               at the tile's nodes (summed over the parts in registers),
+//   Σ W2 (Σ_e v_e p)²                        over the tile's own centres (every row lives in one tile).
+// p (2R halo) and t are staged in LDS with the odd dim-2 stride G.sp.  The columns of a node are
+// contiguous in t, then x: an image row is one contiguous run of global memory, and lanes walk it in
+// that order in the staging loop and in the q update.  The part loop and every sum run in a fixed
+// order, no atomics.  A removed column (the reference epoch) holds p = 0 like everywhere in the step,
+// and its q is never read.  Same stream and place as k_cg_var2d: RMW of q behind the normal kernel and
+// the x-edge pass, before the node gather.
+__global__ __launch_bounds__(BLOCK) void k_cg_scaled(const CgState* __restrict__ st, CgSc G,
+                                                     const CgScPart* __restrict__ parts,
+                                                     const double* __restrict__ W2, const double* __restrict__ p,
+                                                     double* __restrict__ q, double* __restrict__ part) {
+    extern __shared__ double cgs_lds[];
+    if (st && st->stop) return;
+    const int R = G.R, TY = G.ty, SP = G.sp, S2 = G.S2;
+    const int PH = TY + 4 * R, PW = CGS_TX + 4 * R, CH = TY + 2 * R, CW = CGS_TX + 2 * R;
+    double* Pl = cgs_lds;
+    double* Tl = Pl + PH * PW * SP;
+    const int b = blockIdx.x;
+    const int ty = b / G.ntx, tx = b - ty * G.ntx;
+    const int y0 = ty * TY, x0 = tx * CGS_TX;
+    const uint32_t rowlen = (uint32_t)(PW * S2);
+    for (uint32_t i = threadIdx.x; i < (uint32_t)PH * rowlen; i += BLOCK) {
+        const uint32_t ry = i / rowlen, j = i - ry * rowlen;
+        const uint32_t rx = fdiv(j, G.fd_s2), t = j - rx * (uint32_t)S2;
+        const int y = y0 - 2 * R + (int)ry, x = x0 - 2 * R + (int)rx;
+        Pl[(ry * PW + rx) * SP + t] =
+            (y >= 0 && y < G.S0 && x >= 0 && x < G.S1) ? p[(int64_t)G.col0 + ((int64_t)y * G.S1 + x) * S2 + t] : 0.0;
+    }
+    const int nn = TY * CGS_TX * S2;   // ≤ CGS_ITEMS · BLOCK (cg_describe)
+    double qa[CGS_ITEMS];
+#pragma unroll
+    for (int k = 0; k < CGS_ITEMS; ++k) qa[k] = 0.0;
+    double acc = 0.0;
+    for (int qq = 0; qq < G.np; ++qq) {
+        const CgScPart& P = parts[G.part0 + qq];
+        const int W1 = P.hi[1] - P.lo[1];
+        __syncthreads();   // p staged; the previous part's t read
+        for (uint32_t i = threadIdx.x; i < (uint32_t)(CH * CW * S2); i += BLOCK) {
+            const uint32_t cc = fdiv(i, G.fd_s2), t = i - cc * (uint32_t)S2;
+            const int cy = (int)(cc / (uint32_t)CW), cx = (int)cc - cy * CW;
+            const int y = y0 - R + cy, x = x0 - R + cx;
+            double tv = 0.0;
+            if (y >= P.lo[0] && y < P.hi[0] && x >= P.lo[1] && x < P.hi[1] && (int)t >= P.lo[2] && (int)t < P.hi[2]) {
+                double s = 0.0;   // every entry of an existing row lies inside the grid (cg_describe checks it)
+                for (int e = 0; e < P.ntpl; ++e)
+                    s += P.val[e] * Pl[((cy + R + P.oy[e]) * PW + (cx + R + P.ox[e])) * SP + (int)t + P.ot[e]];
+                tv = W2[P.w2 + (int64_t)(y - P.lo[0]) * W1 + (x - P.lo[1])] * s;
+                if (cy >= R && cy < R + TY && cx >= R && cx < R + CGS_TX) acc += tv * s;
+            }
+            Tl[cc * SP + t] = tv;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < CGS_ITEMS; ++k) {
+            const int i = (int)threadIdx.x + k * BLOCK;
+            if (i >= nn) continue;
+            const uint32_t nd = fdiv((uint32_t)i, G.fd_s2);
+            const int t = i - (int)nd * S2, iy = (int)(nd / CGS_TX), ix = (int)(nd % CGS_TX);
+            double s = 0.0;
+            for (int e = 0; e < P.ntpl; ++e) {
+                const int tt = t - P.ot[e];
+                if (tt >= 0 && tt < S2)
+                    s += P.val[e] * Tl[((iy + R - P.oy[e]) * CW + (ix + R - P.ox[e])) * SP + tt];
+            }
+            qa[k] += s;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < CGS_ITEMS; ++k) {
+        const int i = (int)threadIdx.x + k * BLOCK;
+        if (i >= nn) continue;
+        const uint32_t nd = fdiv((uint32_t)i, G.fd_s2);
+        const int t = i - (int)nd * S2, y = y0 + (int)(nd / CGS_TX), x = x0 + (int)(nd % CGS_TX);
+        if (y < G.S0 && x < G.S1) q[(int64_t)G.col0 + ((int64_t)y * G.S1 + x) * S2 + t] += qa[k];
+    }
+    store_partial(acc, part, G.blk0 + b);
+}
+
+inline size_t cg_sc_lds(const CgSc& G) {
+    return sizeof(double) * (size_t)G.sp *
+           ((size_t)(G.ty + 4 * G.R) * (CGS_TX + 4 * G.R) + (size_t)(G.ty + 2 * G.R) * (CGS_TX + 2 * G.R));
+}
+
+// A scaled part's field W2 = rs² over its (y, x) centre box from the row scales (weight × row mask) of
+// its rows at dim-2 position lo2; bad[0] = 1 when some (y, x) holds two scales that differ in a bit
+__global__ __launch_bounds__(BLOCK) void k_cg_sc_field(int32_t row0, int32_t n0, int32_t n1, int32_t n2, int32_t bs0,
+                                                       int32_t bs1, int32_t bs2, const double* __restrict__ rs,
+                                                       double* __restrict__ W2, int32_t* __restrict__ bad) {
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < (int64_t)n0 * n1; i += (int64_t)gridDim.x * BLOCK) {
+        const int64_t yy = i / n1, xx = i - yy * n1;
+        const int64_t r = (int64_t)row0 + yy * bs0 + xx * bs1;
+        const double w = rs[r];
+        bool same = true;
+        for (int k = 1; k < n2; ++k) same = same && __double_as_longlong(rs[r + (int64_t)k * bs2]) == __double_as_longlong(w);
+        if (!same) bad[0] = 1;
+        W2[i] = w * w;
+    }
+}
+
+// q += A_vᵀA_v p for every field-valued part (partials at part + V.blk0), then q += A_qᵀ W2 A_q p for
+// every part with a row scale per (y, x) node, a launch per grid (partials at part + G.blk0)
+struct CgMarks;
+void cg_mark_scaled(CgMarks* m, hipStream_t st);   // the profilers' mark in front of k_cg_scaled (CG_SCALED0)
+void cg_launch_var(const System& S, const double* p, double* q, double* part, hipStream_t st, const CgState* cst,
+                   CgMarks* marks = nullptr) {
     for (const CgVar& V : S.cg_var) {
         const dim3 grid((unsigned)(V.nty * V.ntx));
         if (V.R == 1)
@@ -1577,6 +1685,10 @@ void cg_launch_var(const System& S, const double* p, double* q, double* part, hi
         else
             hipLaunchKernelGGL(k_cg_var2d<2>, grid, dim3(BLOCK), cg_var_lds(V), st, cst, V, p, q, part);
     }
+    if (marks && !S.cg_sc.empty()) cg_mark_scaled(marks, st);
+    for (const CgSc& G : S.cg_sc)
+        hipLaunchKernelGGL(k_cg_scaled, dim3((unsigned)(G.nty * G.ntx)), dim3(BLOCK), cg_sc_lds(G), st, cst, G,
+                           S.cg_scp.p, S.cg_scw.p, p, q, part);
 }
 
 // ---- host: normal-stencil description ------------------------------------------------------
@@ -1588,7 +1700,9 @@ int cls_of(int c, int n, int K, int ncls) { return ncls == n ? c : (c < K ? c : 
 //   (AᵀA)_{c, c+d} = Σ_q w_q² Σ_{t1,t2: o_t2 − o_t1 = d} v_t1 v_t2 · [c − o_t1 ∈ box_q]
 // evaluated at the representative node of each boundary class.  T.on = false for a grid without
 // parts.  False (+ reason) when the structured normal operator does not apply.
-bool ns_from_parts(const MfDesc& d, int g, NsTable& T, std::string& why) {
+// scaled (lsq_set_cg_scaled): a part with per-row scales is left out of the table, as a field-valued one
+// is (k_cg_scaled applies it; cg_describe checks that its scales are one per (y, x) node).
+bool ns_from_parts(const MfDesc& d, int g, NsTable& T, std::string& why, bool scaled = false) {
     const MfGrid& G = d.g[g];
     T = NsTable{};
     for (int e = 0; e < 3; ++e) T.shape[e] = G.shape[e];
@@ -1600,8 +1714,11 @@ bool ns_from_parts(const MfDesc& d, int g, NsTable& T, std::string& why) {
     int K[3] = {0, 0, 0};
     for (int qq = 0; qq < G.nparts; ++qq) {
         const MfPart& P = d.p[G.part[qq]];
-        if (!P.wconst) { why = "a stencil part has per-row scales (masked or non-uniform constraint rows)"; return false; }
-        if (P.var) continue;   // field-valued: k_cg_var2d
+        if (!P.wconst && (!scaled || P.var)) {
+            why = "a stencil part has per-row scales (masked or non-uniform constraint rows)";
+            return false;
+        }
+        if (P.var || !P.wconst) continue;   // field-valued: k_cg_var2d; scaled: k_cg_scaled
         for (int e = 0; e < 3; ++e) {
             int omin = 1 << 20, omax = -(1 << 20);
             for (int t = 0; t < P.ntpl; ++t) {
@@ -1617,7 +1734,7 @@ bool ns_from_parts(const MfDesc& d, int g, NsTable& T, std::string& why) {
                 if (std::find(offs.begin(), offs.end(), dd) == offs.end()) offs.push_back(dd);
             }
     }
-    if (offs.empty()) offs.push_back({0, 0, 0});   // only field-valued parts: a zero class table
+    if (offs.empty()) offs.push_back({0, 0, 0});   // only field-valued or scaled parts: a zero class table
     if ((int)offs.size() > CG_MAX_OFF) { why = "normal stencil wider than CG_MAX_OFF"; return false; }
     std::sort(offs.begin(), offs.end());
     for (int e = 0; e < 3; ++e) {
@@ -1634,7 +1751,7 @@ bool ns_from_parts(const MfDesc& d, int g, NsTable& T, std::string& why) {
                 double* row = T.coef.data() + ((size_t)(cy * T.ncls[1] + cx) * T.ncls[2] + ct) * noff;
                 for (int qq = 0; qq < G.nparts; ++qq) {
                     const MfPart& P = d.p[G.part[qq]];
-                    if (P.var) continue;
+                    if (P.var || !P.wconst) continue;
                     for (int t1 = 0; t1 < P.ntpl; ++t1) {
                         bool in = true;   // the row centred at pos − o_t1 exists
                         for (int e = 0; e < 3; ++e) {
@@ -2029,7 +2146,7 @@ bool cg_describe(System& S, std::string& why) {
     const MfDesc& d = S.mfh;
     std::vector<NsTable> T(d.n_grids);
     for (int g = 0; g < d.n_grids; ++g)
-        if (!ns_from_parts(d, g, T[g], why)) return false;
+        if (!ns_from_parts(d, g, T[g], why, S.cg_scaled)) return false;
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, S.device);
     CgDesc c{};
@@ -2072,6 +2189,105 @@ bool cg_describe(System& S, std::string& why) {
         nvb += V.nty * V.ntx;
         var.push_back(V);
     }
+    // parts with a row scale per (y, x) node (lsq_set_cg_scaled; ns_from_parts left them out of the tables)
+    std::vector<CgSc> scg;
+    std::vector<CgScPart> scp;
+    std::vector<int> scid;
+    int64_t wn = 0;
+    S.cg_sc.clear();
+    S.cg_sc_id.clear();
+    for (int g = 0; g < d.n_grids && S.cg_scaled; ++g) {
+        const MfGrid& G = d.g[g];
+        CgSc C{};
+        C.part0 = (int)scp.size();
+        for (int qq = 0; qq < G.nparts; ++qq) {
+            const int pi = G.part[qq];
+            const MfPart& P = d.p[pi];
+            if (P.wconst || P.var) continue;
+            const std::string who = "stencil part " + std::to_string(pi) + " (grid " + std::to_string(g) + ", rows " +
+                                    std::to_string(P.row0) + " to " + std::to_string(P.row0 + P.n_eq - 1) + ")";
+            if (S.dist || S.virt || S.comm || S.nranks > 1) {
+                why = who + " has per-row scales: lsq_set_cg_scaled is single-GPU, a rank of a distributed, virtual or "
+                            "device group keeps LSQR";
+                return false;
+            }
+            if (!c.colmode) {
+                why = who + " has per-row scales: lsq_set_cg_scaled runs in column mode only, not in tile or chunk mode "
+                            "(16 epochs and more)";
+                return false;
+            }
+            CgScPart Q{};
+            Q.ntpl = P.ntpl;
+            for (int e = 0; e < 3; ++e) {
+                Q.lo[e] = P.lo[e];
+                Q.hi[e] = P.hi[e];
+            }
+            for (int t = 0; t < P.ntpl; ++t) {
+                Q.oy[t] = P.off[t][0];
+                Q.ox[t] = P.off[t][1];
+                Q.ot[t] = P.off[t][2];
+                Q.val[t] = P.val[t];
+                C.R = std::max({C.R, std::abs(Q.oy[t]), std::abs(Q.ox[t])});
+                for (int e = 0; e < 3; ++e)   // k_cg_scaled reads p at every entry of an existing row unchecked
+                    if (P.lo[e] + P.off[t][e] < 0 || P.hi[e] - 1 + P.off[t][e] >= G.shape[e]) {
+                        why = who + " has per-row scales and rows that reach outside the grid";
+                        return false;
+                    }
+            }
+            if (C.R > 2) { why = who + " has per-row scales and reaches beyond ±2 in y or x"; return false; }
+            Q.w2 = wn;
+            wn += (int64_t)(P.hi[0] - P.lo[0]) * (P.hi[1] - P.lo[1]);
+            scp.push_back(Q);
+            scid.push_back(pi);
+        }
+        C.np = (int)scp.size() - C.part0;
+        if (!C.np) continue;
+        C.S0 = G.shape[0];
+        C.S1 = G.shape[1];
+        C.S2 = G.shape[2];
+        C.col0 = G.col0;
+        C.fd_s2 = make_fastdiv((uint32_t)C.S2);
+        C.sp = C.S2 | 1;
+        for (C.ty = 8; C.ty > 1; C.ty /= 2)   // the largest tile whose image fits 64 KB beside the partials' words
+            if (cg_sc_lds(C) + 64 <= 64 * 1024 && C.ty * CGS_TX * C.S2 <= CGS_ITEMS * BLOCK) break;
+        if (cg_sc_lds(C) + 64 > 64 * 1024 || C.ty * CGS_TX * C.S2 > CGS_ITEMS * BLOCK) {
+            why = "per-row scales: a grid's dim-2 column is too long for k_cg_scaled's tile";
+            return false;
+        }
+        C.nty = (C.S0 + C.ty - 1) / C.ty;
+        C.ntx = (C.S1 + CGS_TX - 1) / CGS_TX;
+        C.blk0 = nvb;
+        nvb += C.nty * C.ntx;
+        scg.push_back(C);
+    }
+    if (!scp.empty()) {   // the fields, and the check that a part's scale does not vary along dim 2
+        if (S.cg_scw.n != wn) S.cg_scw.alloc(wn);
+        if (S.cg_scp.n != (int64_t)scp.size()) S.cg_scp.alloc((int64_t)scp.size());
+        S.cg_scp.upload(scp.data(), (int64_t)scp.size(), S.stream);
+        DBuf<int32_t> bad((int64_t)scp.size());
+        bad.zero(S.stream);
+        for (size_t k = 0; k < scp.size(); ++k) {
+            const MfPart& P = d.p[scid[k]];
+            const int n0 = P.hi[0] - P.lo[0], n1 = P.hi[1] - P.lo[1], n2 = P.hi[2] - P.lo[2];
+            hipLaunchKernelGGL(k_cg_sc_field, dim3(grid_for((int64_t)n0 * n1)), dim3(BLOCK), 0, S.stream, P.row0, n0, n1,
+                               n2, P.bstride[0], P.bstride[1], P.bstride[2], S.rs.p, S.cg_scw.p + scp[k].w2, bad.p + k);
+        }
+        KERNEL_CHECK();
+        std::vector<int32_t> hb(scp.size());
+        bad.download(hb.data(), (int64_t)scp.size(), S.stream);
+        HIP_CHECK(hipStreamSynchronize(S.stream));
+        for (size_t k = 0; k < scp.size(); ++k)
+            if (hb[k]) {
+                const MfPart& P = d.p[scid[k]];
+                why = "stencil part " + std::to_string(scid[k]) + " (grid " + std::to_string(P.grid) + ", rows " +
+                      std::to_string(P.row0) + " to " + std::to_string(P.row0 + P.n_eq - 1) +
+                      ") has per-row scales that differ along dim 2 at one (y, x) node: lsq_set_cg_scaled needs one "
+                      "scale per node";
+                return false;
+            }
+    }
+    S.cg_sc = std::move(scg);
+    S.cg_sc_id = std::move(scid);
     S.cg_ns = std::move(T);
     S.cg_var = std::move(var);
     S.cg_nvb = nvb;
@@ -2231,6 +2447,11 @@ bool cg_prepare(System& S, int precond) {
     for (int p = 0; p < S.mfh.n_parts; ++p) {
         key.push_back(S.mfh.p[p].wconst ? S.mfh.p[p].w : NAN);
     }
+    // lsq_set_cg_scaled: a part with per-row scales keeps its description until the row scales are refreshed
+    // (its field is then stale); −(1 + refreshes) is no row scale
+    if (S.cg_scaled)
+        for (double& k : key)
+            if (std::isnan(k)) k = -(double)(1 + S.rs_gen);
     if (!S.cg_ok || key != S.cg_wkey || S.cgd.p == nullptr) {
         graph_cache_drop(&S);   // captured launches hold the table / description pointers
         mg_free(S.mg);          // the multigrid levels are Galerkin products of these tables
@@ -2317,9 +2538,10 @@ inline bool cg_col_order(const System& S) { return S.cgh.colmode || cg_use_dmf(S
 // q = N p (cg_launch_apply): NORMAL, AD, the elimination's E0 … E3 (elim_nbk), XR_FWD and XR_ATQ
 // (xr_active), ATQ; tile mode runs AD, then NORMAL (which adds ATd·t), and nothing else — unless its data
 // rows are matrix-free (cg_tile_dmf): then column mode's order, without the extra rows.  Then
-// cg_launch_update: ALPHA, PRECOND, BETA.  BEGIN stands before the step's first launch.
+// cg_launch_update: ALPHA, PRECOND, BETA.  BEGIN stands before the step's first launch, SCALED0 inside
+// NORMAL in front of k_cg_scaled (with it in the mask, NORMAL's time is that kernel's).
 enum CgStage {
-    CG_BEGIN, CG_NORMAL, CG_AD, CG_E0, CG_E1, CG_E2, CG_E3, CG_XR_FWD, CG_XR_ATQ, CG_ATQ, CG_ALPHA, CG_PRECOND,
+    CG_BEGIN, CG_SCALED0, CG_NORMAL, CG_AD, CG_E0, CG_E1, CG_E2, CG_E3, CG_XR_FWD, CG_XR_ATQ, CG_ATQ, CG_ALPHA, CG_PRECOND,
     CG_BETA, CG_NSTAGE
 };
 constexpr unsigned cg_bit(int stage) { return 1u << stage; }
@@ -2337,6 +2559,8 @@ inline void cg_mark(CgMarks* m, int stage, hipStream_t st) {
     HIP_CHECK(hipEventRecord(m->ev[m->stage.size()], st));
     m->stage.push_back(stage);
 }
+
+void cg_mark_scaled(CgMarks* m, hipStream_t st) { cg_mark(m, CG_SCALED0, st); }
 
 #include "bias.inc"
 #include "sgrid.inc"
@@ -2434,14 +2658,15 @@ void cg_launch_xedge(System& S, const CgGrids& g, const double* pnew, hipStream_
 }
 
 // xedge = false: the caller launches k_cg_xedge itself (cg_launch_iteration runs it on S.side)
-void cg_launch_normal(System& S, const CgGrids& g, const double* pold, double* pnew, bool xedge = true) {
+void cg_launch_normal(System& S, const CgGrids& g, const double* pold, double* pnew, bool xedge = true,
+                      CgMarks* marks = nullptr) {
     const size_t lds = sizeof(double) * S.cgh.lds_max;
     if (S.cgh.colmode) {
         cg_launch_ns(S.cgh, S.cgd.p, S.cg_coefc.p, S.stream, S.cst.p, S.cg_z.p, pold, pnew, S.cg_q.p, S.cg_part_g.p,
                      nullptr);
         if (xedge) {
             cg_launch_xedge(S, g, pnew, S.stream);
-            cg_launch_var(S, pnew, S.cg_q.p, S.cg_part_g.p + g.gN + S.cgh.nedge, S.stream, S.cst.p);
+            cg_launch_var(S, pnew, S.cg_q.p, S.cg_part_g.p + g.gN + S.cgh.nedge, S.stream, S.cst.p, marks);
         }
     } else {   // tile mode, or its tiles cut along dim 2 too (chunk mode): the same arguments, step and partial slots
         const bool atd = !cg_use_dmf(S);   // matrix-free data rows: q = N_s p alone (cg_launch_apply)
@@ -2483,7 +2708,7 @@ void cg_launch_rows(System& S, const CgGrids& g, const double* pold, const doubl
 void cg_launch_apply(System& S, const CgGrids& g, const double* pold, double* pnew, CgMarks* marks = nullptr) {
     cg_mark(marks, CG_BEGIN, S.stream);
     if (cg_col_order(S)) {   // normal (writes p, q = N_s p) → data (t = Ad p) → q += ATd·t
-        cg_launch_normal(S, g, pold, pnew);
+        cg_launch_normal(S, g, pold, pnew, true, marks);
         cg_mark(marks, CG_NORMAL, S.stream);
         cg_launch_rows(S, g, pold, pnew, marks);
     } else {               // data → normal (adds ATd·t)
@@ -2510,7 +2735,7 @@ void cg_launch_update(System& S, const CgGrids& g, int precond, CgMarks* marks =
 void cg_launch_iteration(System& S, const CgGrids& g, int ph, int precond) {
     const double* pold = cg_pold(S, ph);
     double* pnew = cg_pnew(S, ph);
-    if (S.cgh.colmode && cg_use_dmf(S) && S.cg_var.empty() && S.cgh.pad[1] == 8) {
+    if (S.cgh.colmode && cg_use_dmf(S) && S.cg_var.empty() && S.cg_sc.empty() && S.cgh.pad[1] == 8) {
         // the x-edge correction (q at the dim-1 edge nodes, latency-bound) in the data rows'
         // Ad·p launch (both read p only), then q += Adᵀt with α in the node gather's workgroup 0
         cg_launch_normal(S, g, pold, pnew, false);
@@ -2708,6 +2933,14 @@ void cg_run_batch(System& S, int count, bool use_graph, int precond) {
     KERNEL_CHECK();
 }
 
+// k_cg_scaled's launches: p once, q read and written per column of the grids with scaled parts, and
+// every part's field once
+double cg_scaled_bytes(const System& S) {
+    double b = 8.0 * (double)S.cg_scw.n * (S.cg_sc.empty() ? 0.0 : 1.0);
+    for (const CgSc& G : S.cg_sc) b += 24.0 * (double)G.S0 * G.S1 * G.S2;
+    return b;
+}
+
 // Algorithmic HBM bytes per launch (DESIGN.md §CGNR byte model): out = {data, normal, precond}
 void cg_kernel_bytes(const System& S, int precond, double out[3]) {
     const double nf = (double)S.n_full, md = (double)S.mfh.npts, zd = (double)S.GdT.nnz, ne = (double)S.mfh.nodes;
@@ -2736,6 +2969,7 @@ void cg_kernel_bytes(const System& S, int precond, double out[3]) {
     if (xr_active(S)) out[0] += xr_step_bytes(S);
     for (const CgVar& V : S.cg_var)   // field-valued parts: fields + p once, q read and written
         out[1] += (double)V.n_eq * 8.0 * V.nfield + 24.0 * (double)V.S0 * V.S1;
+    out[1] += cg_scaled_bytes(S);
     if (precond == 4 && S.mg) {
         out[2] = mg_bytes(S, out[0] + out[1]);
     } else if (precond == 3) {
@@ -2785,6 +3019,32 @@ void cg_set_chunks(System& S, bool on) {
     S.cg_ok = false;
     S.cg_why.clear();
     S.cg_ready = false;
+}
+
+// lsq_set_cg_scaled: the flag cg_describe hands to ns_from_parts.  A change drops what cg_set_chunks drops.
+void cg_set_scaled(System& S, bool on) {
+    if (S.cg_scaled == on) return;
+    S.cg_scaled = on;
+    graph_cache_drop(&S);
+    mg_free(S.mg);
+    S.mg = nullptr;
+    S.mg_why.clear();
+    S.cg_ok = false;
+    S.cg_why.clear();
+    S.cg_ready = false;
+    S.cg_sc.clear();
+    S.cg_sc_id.clear();
+}
+
+// lsq_cg_scaled_info (builds the description if needed): {scaled parts, bytes of their fields, grids with
+// scaled parts, workgroups of their launches}; zeros without a CGNR operator or without the key
+void cg_scaled_info(System& S, int64_t* out4) {
+    std::fill(out4, out4 + 4, (int64_t)0);
+    if (!cg_prepare(S, 1)) return;
+    out4[0] = (int64_t)S.cg_sc_id.size();
+    out4[1] = S.cg_sc.empty() ? 0 : 8 * S.cg_scw.n;
+    out4[2] = (int64_t)S.cg_sc.size();
+    for (const CgSc& G : S.cg_sc) out4[3] += (int64_t)G.nty * G.ntx;
 }
 
 // lsq_set_cg_tile_dmf: read by build_dmf at the formation (the point table of a long column) and by
@@ -3027,6 +3287,21 @@ void cg_profile_xr(System& S, int reps, int precond, double* out) {
     out[1] = ms[CG_XR_ATQ];
     out[2] = ms[data];
     out[3] = ms[CG_ATQ];
+}
+
+// k_cg_scaled inside real iterations (cg_profile_steps, the mark CG_SCALED0 in front of it): out4 = {ms of
+// its launches (one per grid with scaled parts), their algorithmic bytes, ms of the normal kernel, the
+// x-edge pass and the field-valued parts in front of them, ms of the whole step}, means over reps iterations.
+void cg_profile_scaled(System& S, int reps, int precond, double* out) {
+    cg_need_live(S, precond, "lsq_profile_cg_scaled");
+    if (S.cg_sc.empty()) throw std::invalid_argument("lsq_profile_cg_scaled: no scaled parts in the CGNR operator");
+    double ms[CG_NSTAGE];
+    cg_profile_steps(S, reps, precond,
+                     cg_bit(CG_BEGIN) | cg_bit(CG_SCALED0) | cg_bit(CG_NORMAL) | cg_bit(CG_BETA), ms);
+    out[0] = ms[CG_NORMAL];
+    out[1] = cg_scaled_bytes(S);
+    out[2] = ms[CG_SCALED0];
+    out[3] = ms[CG_SCALED0] + ms[CG_NORMAL] + ms[CG_BETA];
 }
 
 // the elimination's four kernels inside real iterations: out4 = ms of the stages E0 … E3

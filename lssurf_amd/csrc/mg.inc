@@ -1918,6 +1918,8 @@ void mg_tile_kt_table(MgLevel& V, const std::vector<double>& coefc, hipStream_t 
 
 bool mg_build(System& S, std::string& why, const MgDistInfo* di) {
     if (S.dist && !di) { why = "multigrid: a rank builds its levels through the group (lsq_dist_set_global)"; return false; }
+    // lsq_set_cg_scaled: the Galerkin coarse tables of such parts are not class tables any more
+    if (!S.cg_sc.empty()) { why = "multigrid: per-row constraint scales"; return false; }
     if (S.mx && !di && !(S.cgh.colmode && S.dmf.ok)) return mg_build_mixed(S, why);
     if (!S.cg_ok || !S.cgh.colmode) { why = "multigrid: needs the column-mode normal-stencil operator"; return false; }
     if (!cg_use_dmf(S)) { why = "multigrid: needs matrix-free data rows (one shared (y, x) lattice)"; return false; }

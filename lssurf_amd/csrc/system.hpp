@@ -270,6 +270,25 @@ struct CgVar {
     int64_t n_eq;
     const double* F;
 };
+// Stencil parts whose rows carry a row scale per (y, x) node — masked or mapped constraint rows — as the
+// CGNR normal operator applies them under lsq_set_cg_scaled (k_cg_scaled): one workgroup owns a tile of
+// ty × CGS_TX nodes × the whole dim-2 column of a grid and runs over the grid's scaled parts,
+// t = W2 · A_q p at the centres of the tile and its R halo, q += A_qᵀ t, Σ W2 (A_q p)² over the tile's own
+// centres.  W2[(y − lo0)·(hi1 − lo1) + (x − lo1)] = (row scale)² of the part's rows centred at (y, x, ·).
+constexpr int CGS_TX = 16;
+constexpr int CGS_ITEMS = 8;                 // (node, dim 2) items per thread: ty · CGS_TX · S2 ≤ CGS_ITEMS · BLOCK
+struct CgScPart {                            // device resident (System::cg_scp)
+    int32_t ntpl, lo[3], hi[3], pad;
+    int32_t oy[MF_MAXT], ox[MF_MAXT], ot[MF_MAXT];
+    double val[MF_MAXT];
+    int64_t w2;                              // first entry of the part's field in System::cg_scw
+};
+struct CgSc {                                // one grid's scaled parts
+    int32_t S0, S1, S2, col0;
+    int32_t R, ty, sp, np;                   // reach in y and x (≤ 2), tile rows, LDS dim-2 stride (odd), parts
+    int32_t nty, ntx, blk0, part0;           // tiles; first partial slot; first descriptor in cg_scp
+    FastDiv fd_s2;
+};
 struct MgHier;   // multigrid hierarchy (mg.inc)
 void mg_free(MgHier* h);
 void mg_graph_drop(MgHier* h);   // its captured replicated-level V-cycle (ranks)
@@ -628,7 +647,13 @@ struct System {
     DBuf<double> cg_coef, cg_coefc;  // class-row tables: offset-major (tile mode), group × t (column mode)
     std::vector<NsTable> cg_ns;      // host copy of each grid's normal-stencil table (multigrid input)
     std::vector<CgVar> cg_var;       // field-valued parts (k_cg_var2d), partial slots after the x-edge pass
-    int cg_nvb = 0;                  // their workgroups (partial slots)
+    int cg_nvb = 0;                  // their workgroups (partial slots), the scaled parts' included
+    bool cg_scaled = false;          // lsq_set_cg_scaled: parts with a row scale per (y, x) node stay in CGNR
+    std::vector<CgSc> cg_sc;         // grids with such parts (k_cg_scaled), partial slots behind cg_var's
+    std::vector<int> cg_sc_id;       // the parts (indices into mfh.p), in cg_scp's order
+    DBuf<CgScPart> cg_scp;           // their descriptors
+    DBuf<double> cg_scw;             // and squared-scale fields
+    int64_t rs_gen = 0;              // counts the refreshes of the row scales (the fields' staleness key)
     MgHier* mg = nullptr;            // precond 4: geometric multigrid levels (mg.inc), built lazily
     // z0 on a 2× refinement of the dz (y, x) lattice (the reference notebooks' z0 50 m / dz 100 m):
     // the multigrid's level 1 is the system Galerkin-projected onto the dz lattice (z0 restricted

@@ -42,6 +42,14 @@ together with lsq_cg_chunks=True of 20 to 64: tile and chunk mode then take matr
 timing['tile_eliminate'] says whether the last solve ran so.  Still refused with the key: the multigrid,
 priors beside 'eliminate', n_gpus > 1, more than 64 epochs, 20 or more epochs without lsq_cg_chunks; the
 compute_E rules above are unchanged.
+constraint_scaling_maps (a dict: constraint key -> containers.GridData or an array on the grid's (y, x)
+nodes) scales the constraints' expected values as the reference does; the key 'dz' raises
+NotImplementedError.  A non-uniform mask or such maps give the constraint rows one row scale per node, and
+the device then has no class-table CGNR operator: method 1 falls back to LSQR, and lsq_bias='eliminate',
+sensor grids and priors are refused or take the triplet path.  lsq_cg_scaled=True keeps such fits on
+matrix-free CGNR with block-Jacobi (lsq_set_cg_scaled; below 16 epochs, one GPU); lsq_precond=4 then raises
+with the device's reason and 'auto' takes block-Jacobi; timing['cg_scaled'] says whether the last solve
+ran so.
 """
 from time import ctime, time
 
@@ -100,9 +108,14 @@ DEFAULTS = {'reference_epoch': 0, 'W_ctr': 1e4, 'return_fit_objects': False, 'ma
             # on matrix-free data rows (opt-in; 20 and more epochs need lsq_cg_chunks too; below 16 epochs the
             # key does nothing).  Still refused there: multigrid, priors beside 'eliminate', n_gpus > 1, more
             # than 64 epochs; the compute_E rules are unchanged
-            'lsq_tile_eliminate': False}
+            'lsq_tile_eliminate': False,
+            # masked fits and constraint_scaling_maps inside matrix-free CGNR: constraint rows with one row
+            # scale per (y, x) node are applied by their own kernel instead of method 1 falling back to LSQR
+            # (opt-in; below 16 epochs, one GPU, block-Jacobi: the multigrid stays refused; without a
+            # non-uniform mask or maps the key does nothing)
+            'lsq_cg_scaled': False}
 
-OUT_OF_SCOPE = ('lagrangian_coords', 'constraint_scaling_maps', 'mask_file', 'bias_edit_vals')
+OUT_OF_SCOPE = ('lagrangian_coords', 'mask_file', 'bias_edit_vals')
 
 
 class FitSystem:
@@ -111,8 +124,12 @@ class FitSystem:
 
     def __init__(self, G_data, Gc, keep_cols, n_full, device=0, structured=True, grids=None, bias=None,
                  extra_ops=None, extra_csr=None, extra_mg=False, sensor_grids=None, joint=False, iterative=True,
-                 cg_chunks=False, tile_dmf=False):
-        """tile_dmf: tile and chunk mode on matrix-free data rows (LSQSolver.set_cg_tile_dmf), set before the
+                 cg_chunks=False, tile_dmf=False, cg_scaled=False):
+        """cg_scaled: per-row constraint scales inside CGNR (LSQSolver.set_cg_scaled): with row weights that
+        give a stencil part one scale per (y, x) node (a mask with mask_scale, constraint_scaling_maps)
+        method 1 stays CGNR with block-Jacobi, and eliminated biases, sensor grids and extra rows run as on
+        unmasked fits.  Column mode (fewer than 16 epochs) only; precond 4 is refused with the device's reason.
+        tile_dmf: tile and chunk mode on matrix-free data rows (LSQSolver.set_cg_tile_dmf), set before the
         formation: with a dz grid of 16 to 19 epochs, or of 20 to 64 beside cg_chunks, bias and sensor_grids
         are then eliminated as below 16 epochs and this constructor's cg_available question passes.
         Multigrid stays refused there, extra rows take the COO path, and 20 or more epochs without
@@ -163,6 +180,12 @@ class FitSystem:
         self.tile_dmf = bool(tile_dmf)
         if self.tile_dmf:
             self.solver.set_cg_tile_dmf(True)
+        if not isinstance(cg_scaled, (bool, np.bool_)):
+            self.solver.close()
+            raise ValueError(f'FitSystem: cg_scaled must be True or False, not {cg_scaled!r}')
+        self.cg_scaled = bool(cg_scaled)
+        if self.cg_scaled:
+            self.solver.set_cg_scaled(True)
         self.solver.set_col_map(self.n_full, keep_cols)
         m = self.n_data + self.n_con
         extra_ops = list(extra_ops or [])
@@ -221,6 +244,8 @@ class FitSystem:
                     self.solver.set_cg_chunks(True)
                 if self.tile_dmf:
                     self.solver.set_cg_tile_dmf(True)
+                if self.cg_scaled:
+                    self.solver.set_cg_scaled(True)
                 self.solver.set_col_map(self.n_full, keep_cols)
                 desc = None
         self.desc = desc           # the descriptors (bench.py's structured CPU baseline reads them)
@@ -531,8 +556,8 @@ def iterate_fit(data, system, rhs, TCinv, G_data, Gc, in_TSE, timing, args, grid
         try:
             x = system.solve(weight, in_TSE, rhs, x0=x0, **opts)
         except NativeError as e:
-            if opts['precond'] != 4:
-                raise
+            if opts['precond'] != 4 or (args['lsq_precond'] == 4 and 'per-row constraint scales' in str(e)):
+                raise   # lsq_cg_scaled with an explicit lsq_precond=4: the device's refusal, no silent change
             # the multigrid set-up can fail for these weights (e.g. a coarsest level that is not
             # positive definite): the block-Jacobi solve still reaches the same solution
             print(f'smooth_fit: multigrid preconditioner unavailable ({e}); block-Jacobi for the rest of '
@@ -549,6 +574,9 @@ def iterate_fit(data, system, rhs, TCinv, G_data, Gc, in_TSE, timing, args, grid
         # did this solve run CGNR in chunk mode (lsq_cg_chunks on a dz grid of 20 to 64 epochs)?
         timing['cg_chunks'] = bool(getattr(system, 'cg_chunks', False) and system.stats['method'] == 1 and
                                    system.solver.cg_layout_info()['mode'] == 'chunk')
+        # did this solve run CGNR with scaled parts (lsq_cg_scaled on a masked or mapped fit)?
+        timing['cg_scaled'] = bool(getattr(system, 'cg_scaled', False) and system.stats['method'] == 1 and
+                                   system.solver.cg_scaled_info()['parts'] > 0)
         # did this solve eliminate biases or sensor grids in tile or chunk mode (lsq_tile_eliminate, 16 to 64 epochs)?
         timing['tile_eliminate'] = bool(
             getattr(system, 'tile_dmf', False) and system.stats['method'] == 1 and
@@ -816,7 +844,7 @@ def _bias_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, bias_model, m
         try:
             return FitSystem(G_grid, Gc_grid, keep_cols[keep_cols < n_grid], n_grid, device=device, grids=grids,
                              bias=bias, sensor_grids=sg, joint=sg is not None, cg_chunks=args['lsq_cg_chunks'],
-                             tile_dmf=args['lsq_tile_eliminate'])
+                             tile_dmf=args['lsq_tile_eliminate'], cg_scaled=args['lsq_cg_scaled'])
         except NativeError as e:
             if mode == 'eliminate':
                 raise
@@ -824,7 +852,7 @@ def _bias_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, bias_model, m
                 warnings.warn(f"smooth_fit: lsq_bias='auto' with lsq_sgrid_joint takes 'columns': the device refuses "
                               f"the joint elimination ({e})", RuntimeWarning, stacklevel=3)
     return FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=device, grids=grids, cg_chunks=args['lsq_cg_chunks'],
-                     tile_dmf=args['lsq_tile_eliminate'])
+                     tile_dmf=args['lsq_tile_eliminate'], cg_scaled=args['lsq_cg_scaled'])
 
 
 def _sgrid_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, sgrid_sensor, constraint_op_list, mode, grids,
@@ -846,12 +874,38 @@ def _sgrid_fit_system(G_data, Gc, G_grid, Gc_grid, keep_cols, data, sgrid_sensor
         try:
             return FitSystem(G_grid, Gc_grid, keep_cols[keep_cols < n_grid], n_grid, device=device, grids=grids,
                              sensor_grids=sg, cg_chunks=args['lsq_cg_chunks'],
-                             tile_dmf=args['lsq_tile_eliminate'])
+                             tile_dmf=args['lsq_tile_eliminate'], cg_scaled=args['lsq_cg_scaled'])
         except NativeError:
             if mode == 'eliminate':
                 raise
     return FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=device, grids=grids, cg_chunks=args['lsq_cg_chunks'],
-                     tile_dmf=args['lsq_tile_eliminate'])
+                     tile_dmf=args['lsq_tile_eliminate'], cg_scaled=args['lsq_cg_scaled'])
+
+
+def _constraint_scaling_masks(maps, grids):
+    """constraint_scaling_maps on the grids' (y, x) nodes (smooth_fit.py:467-485): keys with 'z0' on the z0
+    lattice, the rest on the dz lattice, non-finite entries 1.  A map is a containers.GridData (interpolated
+    to the nodes) or an array already on them.  The key 'dz' (the dz_zero rows) stays outside lssurf_amd."""
+    if maps is None:
+        return None
+    if not isinstance(maps, dict):
+        raise ValueError('smooth_fit: constraint_scaling_maps must be a dict of maps by constraint key')
+    masks = {}
+    for key, this_map in maps.items():
+        if key == 'dz':
+            raise NotImplementedError("smooth_fit: constraint_scaling_maps['dz'] (the dz_zero rows) is outside "
+                                      "lssurf_amd (SURVEY.md §2)")
+        grid = grids['z0'] if 'z0' in key else grids['dz']
+        if hasattr(this_map, 'interp'):
+            mask = np.array(this_map.interp(grid.ctrs[1], grid.ctrs[0], gridded=True), dtype=float)
+        else:
+            mask = np.array(this_map, dtype=float)
+        if mask.shape != tuple(grid.shape[:2]):
+            raise ValueError(f'smooth_fit: constraint_scaling_maps[{key!r}] has shape {mask.shape}, the grid\'s '
+                             f'(y, x) nodes are {tuple(grid.shape[:2])}')
+        mask[~np.isfinite(mask)] = 1.
+        masks[key] = mask
+    return masks
 
 
 def smooth_fit(**kwargs):
@@ -884,6 +938,8 @@ def smooth_fit(**kwargs):
         raise ValueError(f"smooth_fit: lsq_sgrid_joint must be True or False, not {args['lsq_sgrid_joint']!r}")
     if not isinstance(args['lsq_cg_chunks'], (bool, np.bool_)):
         raise ValueError(f"smooth_fit: lsq_cg_chunks must be True or False, not {args['lsq_cg_chunks']!r}")
+    if not isinstance(args['lsq_cg_scaled'], (bool, np.bool_)):
+        raise ValueError(f"smooth_fit: lsq_cg_scaled must be True or False, not {args['lsq_cg_scaled']!r}")
     if not isinstance(args['lsq_tile_eliminate'], (bool, np.bool_)):
         raise ValueError(f"smooth_fit: lsq_tile_eliminate must be True or False, not {args['lsq_tile_eliminate']!r}")
     bias_mode = args['lsq_bias']
@@ -993,7 +1049,8 @@ def smooth_fit(**kwargs):
     constraint_op_list = []
     if args['VERBOSE']:
         print(f"smooth_fit: E_RMS={args['E_RMS']}")
-    setup_smoothness_constraints(grids, constraint_op_list, args['E_RMS'], args['mask_scale'])
+    setup_smoothness_constraints(grids, constraint_op_list, args['E_RMS'], args['mask_scale'],
+                                 scaling_masks=_constraint_scaling_masks(args['constraint_scaling_maps'], grids))
     zero_prior = set()   # priors created here are zeros: rhs is already zero on their rows
     for op in constraint_op_list:
         if op.prior is None:
@@ -1133,7 +1190,7 @@ def smooth_fit(**kwargs):
                 system = FitSystem(G_data, Gc, keep_cols, Gc.col_N, device=devices[0], grids=grids,
                                    extra_ops=prior_ops, extra_mg=bool(args['lsq_prior_mg']) and bool(prior_ops),
                                    iterative=not dense, cg_chunks=args['lsq_cg_chunks'],
-                                   tile_dmf=args['lsq_tile_eliminate'])
+                                   tile_dmf=args['lsq_tile_eliminate'], cg_scaled=args['lsq_cg_scaled'])
             if b_rows_all is not None and not getattr(system, 'n_extra', 0):
                 b_rows = max(b_rows, b_rows_all)
             if b_rows_sg is not None and getattr(system, 'sg', None) is None:

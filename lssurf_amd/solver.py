@@ -266,6 +266,33 @@ class LSQSolver:
         drops the CGNR description, the captured iterations and the multigrid levels."""
         self._check(self._L.lsq_set_cg_chunks(self._h, 1 if on else 0), 'lsq_set_cg_chunks')
 
+    def set_cg_scaled(self, on=True):
+        """Per-row constraint scales inside CGNR (lsq_set_cg_scaled): a stencil part whose rows carry one
+        row scale per (y, x) node — the constraint rows of a masked fit or of constraint_scaling_maps — is
+        applied by its own kernel instead of the refusal that sends method 1 to LSQR.  Column mode (fewer
+        than 16 epochs) and single-GPU handles only; the multigrid stays refused.  Systems without such
+        parts are unchanged.  A change drops the CGNR description, the captured iterations and the
+        multigrid levels."""
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError(f'set_cg_scaled: on must be True or False, not {on!r}')
+        self._check(self._L.lsq_set_cg_scaled(self._h, 1 if on else 0), 'lsq_set_cg_scaled')
+
+    def cg_scaled_info(self):
+        """The scaled parts of the CGNR operator (lsq_cg_scaled_info; builds the description if needed):
+        their number, the bytes of their squared-scale fields, the grids that hold them and the
+        workgroups of their launches.  Zeros without set_cg_scaled or without a CGNR operator."""
+        o = np.zeros(4, np.int64)
+        self._check(self._L.lsq_cg_scaled_info(self._h, ptr(o)), 'lsq_cg_scaled_info')
+        return dict(zip(['parts', 'field_bytes', 'grids', 'workgroups'], (int(v) for v in o)))
+
+    def profile_cg_scaled(self, reps=20, precond=3):
+        """Device time (ms) of the scaled parts' kernel inside real iterations (after iterate() with the
+        same precond), its byte model, the time of the normal kernel and x-edge pass before it and of
+        the whole step."""
+        o = np.zeros(4)
+        self._check(self._L.lsq_profile_cg_scaled(self._h, int(reps), int(precond), ptr(o)), 'lsq_profile_cg_scaled')
+        return dict(zip(['k_cg_scaled', 'bytes', 'normal_before', 'step'], o.tolist()))
+
     def cg_layout_info(self):
         """The normal operator's layout (lsq_cg_layout_info; builds the description if needed): mode
         ('none' with its reason, 'column', 'tile' or 'chunk'), and of the grid with the longest last
